@@ -2,16 +2,19 @@
 """Benchmark of the hot path: one training step = event batch -> poses -> rays -> sampling ->
 hash grid -> fused MLPs -> compositing -> event loss -> backward -> (all-reduce) -> Adam.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1 is launched by the driver through torch.distributed.run (one process per GPU, RCCL).
 Workload = BASELINE.json configs[1] as SURVEY.md 8 defines config B: synthetic 'ficus'-like event stream, R = 65 536
 rays PER RENDER x 128 samples, i.e. 65 536 events per step whose two renders (start / end timestamps) run as one
 131 072-ray pass (n = 16 777 216 samples per kernel launch), fp32, default synthetic.yaml NGP model.
 `--events 32768` is the other reading (65 536 rays per STEP, n = 8 388 608 per launch; profiles/rNN_bench_half.json).
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
-kernel (HIP-event timed inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded
-sample of the same workload, rank 0, N = 1 only).
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, ...).
+`--full` adds, after the timed steps: `kernels` and `roofline` for the dominant kernel (HIP events per launch over eager
+steps behind the timed region), `strong_scaling` (N > 1) and `cpu_baseline` (the CPU oracle on a bounded sample of the
+same workload, rank 0, N = 1 only, unless --no-cpu-baseline).
+`--dump-outputs DIR` writes what the last timed step left to its caller as DIR/<name>.npy (dump_outputs): inputs are
+seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -186,6 +189,44 @@ def cpu_baseline(args, scene, params_cpu, table_seed):
                       f"{torch.get_num_threads()} torch threads on {n_cpu} logical CPUs ({model})"}
 
 
+DUMP_PARAMS_MAX = 1 << 22        # --dump-outputs: parameters in full up to 4 M entries, above that a fixed sample of 4 M
+DUMP_PER_RAY_MAX = 1 << 20       # per-ray outputs likewise, 1 M entries each: at most ~40 MB in all
+
+
+def _host_array(x, cap):
+    """x (a device tensor) as a float32 / float64 numpy array: whole, or -- above `cap` entries -- the entries at a fixed,
+    seeded, sorted sample of `cap` flat indices (the same indices in every run of the same shape)"""
+    x = torch.as_tensor(x).detach()
+    if x.numel() > cap:
+        idx = np.sort(np.random.default_rng(0).choice(x.numel(), cap, replace=False))
+        x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+    a = x.cpu().numpy()
+    return a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+
+
+def dump_outputs(path, loss, aux, tr):
+    """What the caller of the timed step holds after its last step, as <path>/<name>.npy: the loss, the per-ray outputs of
+    the renders (intensity_start / intensity_end / opacity of Trainer.forward_backward; grad_intensity / grad_dlog_dt of the
+    l_grad render), and the parameters the optimiser step left: the field's flat block (`params`: hash table | MLP for the
+    NGP field, sampled above DUMP_PARAMS_MAX), the MLP block alone (`mlp`, NGP field), the background, C_p-ratio and
+    refractory-period parameters."""
+    os.makedirs(path, exist_ok=True)
+    f = tr.r.field
+    out = {"loss": torch.as_tensor(loss).reshape(1)}
+    for k in ("intensity_start", "intensity_end", "opacity"):
+        out[k] = aux[k]
+    if aux.get("grad") is not None:
+        out["grad_intensity"], out["grad_dlog_dt"] = aux["grad"]["intensity"], aux["grad"]["dlog_dt"]
+    out["params"] = f.flat[: f.n_params]
+    if getattr(f, "n_table", None) is not None:
+        out["mlp"] = f.mlp
+    out["background_raw"] = tr.small
+    out["contrast_threshold_raw"] = tr.ct[:1]
+    out["refractory_period_raw"] = tr._tau_raw_dev
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), _host_array(v, DUMP_PARAMS_MAX if k == "params" else DUMP_PER_RAY_MAX))
+
+
 def main():
     # stdout carries exactly ONE line, the JSON result: native libraries that write to file descriptor 1 (RCCL prints a version
     # banner there when its process group goes away) are sent to stderr for the life of the process
@@ -255,7 +296,13 @@ def main():
     ap.add_argument("--graph", default="auto", choices=["auto", "off"],
                     help="auto: occupancy-sampled steps with device-side counts go through Trainer.step, which captures a repeating "
                          "step in a hipGraph and replays it as one launch (Trainer._graph_step); off: every launch from Python")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel HIP-event times and "
+                         "the roofline of the dominant kernel (eager steps behind the timed region), strong scaling (N > 1) "
+                         "and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, per-ray outputs, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
     import faulthandler
@@ -428,7 +475,7 @@ def main():
         if args.loss_grad > 0:
             lg, aux_g = tr.grad_loss_forward_backward(b, j2, early={"inorder": False, "begun": True, "early": "all"}[gmode])
             loss = loss + lg
-            aux = dict(aux, n=aux["n"] + aux_g["n"], rays=aux["rays"] + aux_g["rays"], n_main=aux["n"])
+            aux = dict(aux, n=aux["n"] + aux_g["n"], rays=aux["rays"] + aux_g["rays"], n_main=aux["n"], grad=aux_g)
         tr.optimizer_step()
         return loss, aux
 
@@ -464,33 +511,32 @@ def main():
             log("warmup step", i)
     barrier()
     tr._replays_before = getattr(tr, "graph_replays", 0)
-    ops.profile_start()
     t0 = time.perf_counter()
-    n_samples = n_main = 0
+    n_samples = 0
     for i in range(args.steps):
         loss, aux = one_step(i)
         n_samples += aux["n"]
-        n_main += aux.get("n_main", aux["n"])        # samples seen by the profiled (non-tangent) kernel families
     barrier()
     dt = time.perf_counter() - t0
-    prof = ops.profile_stop()
     log("timed region done", dt)
-    graph_replays, n_main_timed = getattr(tr, "graph_replays", 0), n_main
-    roof_note = None
-    if graph_replays - tr._replays_before > 0:
-        # the timed steps were hipGraph replays: no launch went through the Python wrappers, so there were no per-launch HIP
-        # events.  The dominant call is timed over a few EAGER steps of the same workload right behind the timed region.
+    graph_replays = getattr(tr, "graph_replays", 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, aux, tr)
+    loss = float(loss)
+    if args.full:
+        # per-launch HIP events are kept out of the timed steps: the kernel families are timed over EAGER steps of the same
+        # workload right behind the timed region (hipGraph replays would not go through the Python wrappers at all)
+        replayed = graph_replays - tr._replays_before > 0
         tr.use_graph = False
         ops.profile_start()
-        n_main, k_prof = 0, min(5, args.steps)
+        n_main, k_prof = 0, min(5, args.steps) if replayed else args.steps
         for i in range(k_prof):
             _, aux_p = one_step(args.steps + i)
-            n_main += aux_p.get("n_main", aux_p["n"])
+            n_main += aux_p.get("n_main", aux_p["n"])      # samples seen by the profiled (non-tangent) kernel families
         prof = ops.profile_stop()
-        roof_note = f"launch times: HIP events over {k_prof} eager steps behind the timed region (the {args.steps} timed steps are hipGraph replays)"
+        roof_note = (f"launch times: HIP events over {k_prof} eager steps behind the timed region" +
+                     (f" (the {args.steps} timed steps are hipGraph replays)" if replayed else ""))
         prof_steps = k_prof
-    else:
-        prof_steps = args.steps
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -504,7 +550,7 @@ def main():
     # GLOBAL batch (train_eff_ray_sample_batch_size // num_gpus, robust_e_nerf.py:63-66): every rank takes events // N.
     # One driver run per N then yields both curves.
     strong = None
-    if world > 1 and args.scaling == "weak" and not rccl_single:
+    if args.full and world > 1 and args.scaling == "weak" and not rccl_single:
         B_weak = B
         B = max(1, args.events // world)
         batches = []
@@ -532,14 +578,14 @@ def main():
                   "mlp_samples_per_sec": float(dts[1]) / float(tmax), "steps": args.steps, "warmup": args.warmup}
         B = B_weak
 
-    if "hashgrid_bwd_binned_finish" in prof:
+    if args.full and "hashgrid_bwd_binned_finish" in prof:
         # the phased call of the chunked backward (begin, one scatter per chunk -- timed on the second stream, i.e. while it
         # shares the chip with the MLP backward --, finish) counts as ONE launch of the C-ABI call per backward pass
         calls = prof["hashgrid_bwd_binned_finish"][0]
         total = sum(prof.pop(k)[1] for k in ("hashgrid_bwd_binned_begin", "hashgrid_bwd_binned_scatter", "hashgrid_bwd_binned_finish"))
         c0, m0 = prof.get("hashgrid_bwd_binned", (0, 0.0))
         prof["hashgrid_bwd_binned"] = (c0 + calls, m0 + total)
-    if rank == 0:
+    if rank == 0 and args.full:
         kern = {k: {"launches": c, "avg_ms": ms / max(c, 1)} for k, (c, ms) in prof.items()}
         dom = max(list(BYTES) + list(FLOPS), key=lambda k: prof.get(k, (0, 0.0))[1])
         c, ms = prof.get(dom, (1, 1e-9))                 # degenerate runs (no sample at all) launch none of them
@@ -574,6 +620,7 @@ def main():
                 # the fused arch-mlp kernels move their saved copies through HBM: how close the same call is to the HBM peak
                 roof["hbm_traffic_gbs"] = roof["traffic"] / (per * 1e-3) / 1e9
                 roof["hbm_traffic_frac_of_peak"] = roof["hbm_traffic_gbs"] / HBM_PEAK_GBS
+    if rank == 0:
         out = {
             "metric": "train_rays_per_sec", "value": rays / dt, "unit": "rays/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -611,12 +658,13 @@ def main():
                        "dist_backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else ""))
                        if dist.is_initialized() else None,
                        "gradient_allreduce_bytes_per_step": int(r.field.grad_all.numel() * 4) if dp_world > 1 else 0},
-            "roofline": dict(roof, **({"note": roof_note} if roof_note else {})),
-            "kernels": kern,
         }
+        if args.full:
+            out["roofline"] = dict(roof, note=roof_note)
+            out["kernels"] = kern
         if strong is not None:
             out["strong_scaling"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, scene, {k: v.clone() for k, v in p.items()}, 0)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1 or rccl_single:

@@ -1037,8 +1037,23 @@ def gen_eval_dataset(datasets_mod):
     save("eval_dataset", **out)
 
 
+def gen_train_configs():
+    """The reference's shipped training configs (configs/train/*.yaml) as parsed settings: one JSON string per file, keyed
+    by the file's stem (test_reference_train_yamls_are_accepted_by_the_cli_schema)."""
+    import glob
+    import json
+    import yaml
+    out = {}
+    for f in sorted(glob.glob(os.path.join(REF, "configs", "train", "*.yaml"))):
+        with open(f) as fh:
+            out[os.path.splitext(os.path.basename(f))[0]] = np.array(json.dumps(yaml.safe_load(fh)))
+    save("train_configs", **out)
+
+
 def main():
     assert os.path.isdir(REF), "golden vectors can only be regenerated where /root/reference exists"
+    if sys.argv[1:] == ["train_configs"]:
+        return gen_train_configs()
     install_stubs()
     import nerfacc
     from robust_e_nerf.external import ngp, sh_encoder, vol_rendering
@@ -1085,6 +1100,7 @@ def main():
     gen_posed_images(datasets_mod)
     gen_eval_epoch(rmod)
     gen_eval_dataset(datasets_mod)
+    gen_train_configs()
 
 
 if __name__ == "__main__":

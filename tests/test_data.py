@@ -225,19 +225,16 @@ def test_update_train_batch_size_vs_reference_fixture():
 
 def test_reference_train_yamls_are_accepted_by_the_cli_schema():
     """Every configs/train/*.yaml the reference ships carries the keys scripts/train.py reads and only settings the fused
-    kernels implement (check_supported).  Runs where /root/reference exists (this container); the GPU-side CLI tests use the
-    repo's own files with the same settings."""
-    import glob, os, sys
-    import pytest, yaml
-    ref = "/root/reference/configs/train"
-    if not os.path.isdir(ref):
-        pytest.skip("reference checkout not present")
+    kernels implement (check_supported).  The configs as parsed settings, one JSON string per file (fixture
+    train_configs.npz written by tests/golden/make_golden.py::gen_train_configs); the GPU-side CLI tests use the repo's own
+    files with the same settings."""
+    import json, os, sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
     import train as cli
-    files = sorted(glob.glob(os.path.join(ref, "*.yaml")))
-    assert len(files) >= 4
-    for f in files:
-        cfg = yaml.safe_load(open(f))
+    g = np.load(os.path.join(GOLD, "train_configs.npz"))
+    assert len(g.files) >= 4
+    for f in g.files:
+        cfg = json.loads(str(g[f]))
         ncfg = cfg["model"]["nerf"]
         cli.check_supported(ncfg, ncfg.get("arch", "ngp"))
         cli.check_supported(ncfg, "mlp")

@@ -1341,7 +1341,7 @@ def test_bayer_sensor_step_vs_oracle(amd, spec, full_table_cache):
     nb["u_grad"] = torch.rand(B, generator=gen, dtype=torch.float64).numpy()
     ch = torch.randint(0, 3, (B,), generator=gen)
     p = field.init_params(spec, radiance_dim=3, seed=3)
-    p["hash"] = full_table_cache(7, 0.5)
+    p["hash"] = full_table_cache(7, 0.5).clone()          # (its gradient is taken below: not on the session's cached table)
     bk_raw = torch.tensor([0.3, 0.6, 0.9])
     fld = engine.NGPField(DEV, 3)
     fld.load(p)
@@ -2322,7 +2322,7 @@ def test_bench_n_rank_contract_selftest():
     env = dict(os.environ, REN_BENCH_DIST="gloo:shared-gpu")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29517", os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2",
-                          "--warmup", "1", "--events", "2048"], capture_output=True, text=True, timeout=600, env=env, cwd=repo)
+                          "--warmup", "1", "--events", "2048", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -2346,6 +2346,35 @@ def test_bench_data_parallel_step_over_rccl_single_rank():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["config"]["collectives_per_step"] == 3 and d["value"] > 0 and d["loss"] == d["loss"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench run prints the headline line only (no --full figures) and --dump-outputs writes the last timed step's
+    outputs as float32 / float64 .npy files: the loss in the line, the same arrays from two runs with the same arguments
+    up to the run-to-run repeatability of the step (float atomics of the hash-grid scatter, carried through four Adam steps:
+    ~1e-5 of the table's scale at most; a wrong ray or a different input moves them by far more)."""
+    import json, os, subprocess, sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d_out = os.path.join(tmp_path, f"out{k}")
+        out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--events", "2048", "--dump-outputs", d_out], capture_output=True, text=True, timeout=600, cwd=repo)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append((json.loads(lines[0]), {f[:-4]: np.load(os.path.join(d_out, f)) for f in os.listdir(d_out)}))
+    for d, arrs in runs:
+        assert d["metric"] == "train_rays_per_sec" and d["unit"] == "rays/s" and d["higher_is_better"] is True
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+        assert not {"roofline", "kernels", "cpu_baseline", "strong_scaling"} & set(d)
+        assert {"loss", "intensity_start", "intensity_end", "opacity", "params", "mlp"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["intensity_start"].shape == (2048,) and float(arrs["loss"][0]) == d["loss"]
+    (_, a0), (_, a1) = runs
+    for k in a0:
+        assert a0[k].shape == a1[k].shape and rel_err(a1[k], a0[k]) < 1e-3, k
 
 
 def test_prefetched_step_front_gives_the_same_steps(amd, full_table_cache):

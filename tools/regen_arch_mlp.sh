@@ -21,9 +21,9 @@ done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_arch_mlp_lossgrad_bf16 -o x -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --arch mlp --events 4096 --loss-grad 1e-3 --mlp-bf16 > /dev/null 2>&1
 python $R/tools/summarize_profile.py $(find $O/prof_arch_mlp_lossgrad_bf16 -name '*kernel_stats.csv' | head -1) $R/profiles/${RND}_bench_arch_mlp_lossgrad_bf16_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --arch mlp --events 4096 --loss-grad 1e-3 --mlp-bf16 (1.05 M + 0.52 M samples per step)"
 cd $R
-python bench.py --no-cpu-baseline --arch mlp --events 4096 > profiles/${RND}_bench_arch_mlp.json 2> $O/am.err
-python bench.py --no-cpu-baseline --arch mlp --events 4096 --mlp-bf16 > profiles/${RND}_bench_arch_mlp_bf16.json 2>> $O/am.err
-python bench.py --no-cpu-baseline --arch mlp --events 4096 --mlp-kernels f32 > profiles/${RND}_bench_arch_mlp_f32mfma.json 2>> $O/am.err
-python bench.py --no-cpu-baseline --arch mlp --events 4096 --mlp-precision high > profiles/${RND}_bench_arch_mlp_precision_high.json 2>> $O/am.err
-python bench.py --no-cpu-baseline --arch mlp --events 4096 --loss-grad 1e-3 --mlp-precision high > profiles/${RND}_bench_arch_mlp_lossgrad_precision_high.json 2>> $O/am.err
+python bench.py --full --no-cpu-baseline --arch mlp --events 4096 > profiles/${RND}_bench_arch_mlp.json 2> $O/am.err
+python bench.py --full --no-cpu-baseline --arch mlp --events 4096 --mlp-bf16 > profiles/${RND}_bench_arch_mlp_bf16.json 2>> $O/am.err
+python bench.py --full --no-cpu-baseline --arch mlp --events 4096 --mlp-kernels f32 > profiles/${RND}_bench_arch_mlp_f32mfma.json 2>> $O/am.err
+python bench.py --full --no-cpu-baseline --arch mlp --events 4096 --mlp-precision high > profiles/${RND}_bench_arch_mlp_precision_high.json 2>> $O/am.err
+python bench.py --full --no-cpu-baseline --arch mlp --events 4096 --loss-grad 1e-3 --mlp-precision high > profiles/${RND}_bench_arch_mlp_lossgrad_precision_high.json 2>> $O/am.err
 cp profiles/${RND}_*arch_mlp* $O/; ls $O

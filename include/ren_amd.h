@@ -761,6 +761,19 @@ int ren_vanilla_heads_bwd_jvp(const float *g_rgb, const float *g_rgbd, const flo
                               const float *rgb, const float *sigma, const float *zod, const float *zsd, int64_t n, int32_t C, int32_t activations,
                               float *dz_rgb, float *dzd_rgb, float *dz_sigma, float *dzd_sigma, void *stream);
 
+/* ---- evaluation metrics (csrc/ren_metrics.hip) ------------------------------------------------------- *
+ * SSIM as the reference's validation / test epochs score every aligned view (loss_metric/metric.py:74-81: torchmetrics
+ * ssim, 11 x 11 Gaussian window of sigma 1.5, k1 = 0.01, k2 = 0.03, data_range = the target's largest pixel value; the
+ * epoch value is the mean over the views, robust_e_nerf.py:684-696).  A plane is one (view, channel) image: pred / target
+ * are contiguous (P, H, W) float32 and out[p] (float64) is the mean SSIM over plane p's (H - 10) x (W - 10) valid windows --
+ * torchmetrics reflect-pads by 5, filters and crops 5 pixels per border, so the padding never reaches the mean.  Moments
+ * are filtered in fp64.  One launch scores all planes; deterministic (no atomics), repeated calls are bitwise equal.
+ * REN_ERR_BAD_ARG for a null pointer, P < 1, H or W < 11 (no valid window) or a data_range that is not finite and > 0.
+ * scratch: ren_ssim_scratch_doubles(P, H, W) doubles of device memory (0 for a shape that has no valid window). */
+int64_t ren_ssim_scratch_doubles(int64_t P, int32_t H, int32_t W);
+int ren_ssim_planes(const float *pred, const float *target, int64_t P, int32_t H, int32_t W, double data_range,
+                    double *out, double *scratch, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

@@ -152,6 +152,8 @@ SIGNATURES = {
     "ren_weight_norm_bwd": (c_int, [P, P, P, P, c_int32, c_int64, P, P, c_int32, P]),
     "ren_grad_loss_fwd": (c_int, [P, P, P, P, c_int64, c_int32, P, P]),
     "ren_grad_loss_bwd": (c_int, [P, P, P, P, c_int64, c_int32, c_float, P, P, P, P, P, P]),
+    "ren_ssim_scratch_doubles": (c_int64, [c_int64, c_int32, c_int32]),
+    "ren_ssim_planes": (c_int, [P, P, c_int64, c_int32, c_int32, c_double, P, P, P]),
 }
 
 _lib = None

@@ -3,8 +3,8 @@
 Mirrors ``RobustENeRF.evaluation_step`` / ``render_pixels`` (robust_e_nerf/models/robust_e_nerf.py:
 533-571, 849-885): one camera pose, a full pixel grid, rays rendered in chunks of
 ``test_chunk_size`` without jitter (external/utils.py:99-105,115), then the affine alignment in
-log space and PSNR of ``evaluation_epoch_end`` (:634-677) / ``Metric.compute`` (loss_metric/metric.py:60-72).
-The render runs on the HIP kernels; alignment / PSNR are a handful of reductions on (H*W,) tensors.
+log space and PSNR / SSIM of ``evaluation_epoch_end`` (:634-696) / ``Metric.compute`` (loss_metric/metric.py:60-81).
+The render and SSIM run on the HIP kernels; alignment / L1 / PSNR are a handful of reductions on (H*W,) tensors.
 """
 from __future__ import annotations
 
@@ -180,6 +180,39 @@ def l1(pred: torch.Tensor, target: torch.Tensor) -> float:
     return float((pred.double() - target.double()).abs().mean())
 
 
+def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float, batched: bool = False) -> torch.Tensor:
+    """torchmetrics.functional.ssim(preds, target, data_range=max_target_val) of metric.py:74-81, per view, on the HIP kernel
+    (ops.ssim_planes): (H, W) or (C, H, W) is one view; (V, C, H, W) -- or (V, H, W) with ``batched`` -- are V views.  A
+    view's value is the mean over its channels and its (H - 10) x (W - 10) valid windows.  -> (V,) float64 on pred's device"""
+    if pred.shape != target.shape:
+        raise ValueError(f"ssim: prediction {tuple(pred.shape)} vs target {tuple(target.shape)}")
+    if pred.dim() == 2 or (pred.dim() == 3 and not batched):
+        pred, target = pred.reshape(1, -1, *pred.shape[-2:]), target.reshape(1, -1, *target.shape[-2:])
+    elif pred.dim() == 3:
+        pred, target = pred[:, None], target[:, None]
+    elif pred.dim() != 4:
+        raise ValueError(f"ssim: (H, W), (C, H, W) or (V, [C,] H, W) images; got {tuple(pred.shape)}")
+    V, C, H, W = pred.shape
+    if H < 11 or W < 11:                                   # no valid 11 x 11 window: torchmetrics' mean over nothing
+        return torch.full((V,), float("nan"), dtype=torch.float64, device=pred.device)
+    planes = ops.ssim_planes(pred.reshape(V * C, H, W).float(), target.reshape(V * C, H, W).float(), data_range)
+    return planes.view(V, C).mean(1)
+
+
+def prediction_png(img: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    """8-bit prediction image of robust_e_nerf.py:736-780 (PREDICTION_BIT_DEPTH 8): round(255 clamp((x - lo) / (hi - lo), 0, 1))
+    of an aligned (H, W) or (C, H, W) image -> uint8 (H, W) or (H, W, C) on the CPU"""
+    u8 = (255 * ((img.cpu() - lo) / (hi - lo)).clamp(min=0, max=1)).round().to(torch.uint8)
+    return u8 if u8.dim() == 2 else u8.permute(1, 2, 0).contiguous()
+
+
+def save_prediction(img: torch.Tensor, lo: float, hi: float, path: str) -> None:
+    """grayscale as mode L, a Bayer sensor's (3, H, W) as RGB (the reference writes BGR through cv2, i.e. the same file)"""
+    from PIL import Image
+    u8 = prediction_png(img, lo, hi).numpy()
+    Image.fromarray(u8, mode="L" if u8.ndim == 2 else "RGB").save(path)
+
+
 def align_and_score(pred: torch.Tensor, target: torch.Tensor, data_range: float, sums: Optional[torch.Tensor] = None):
     """evaluation_epoch_end's metric part (robust_e_nerf.py:634-696): `pred`, `target` (V, H, W) or (V, 3, H, W).
     ONE scale / offset per channel fitted over all views (``sums``: the fit's sums when the views of other ranks take part
@@ -194,22 +227,27 @@ def align_and_score(pred: torch.Tensor, target: torch.Tensor, data_range: float,
 
 @torch.no_grad()
 def evaluate_posed_images(r: Renderer, posed: dict, bkgd: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
-                          group=None, chunk: Optional[int] = None, limit: Optional[int] = None):
-    """validation / test epoch of the reference (models/robust_e_nerf.py:519-696) over data.load_posed_images(...): every
+                          group=None, chunk: Optional[int] = None, limit: Optional[int] = None, save_dir: Optional[str] = None):
+    """validation / test epoch of the reference (models/robust_e_nerf.py:519-780) over data.load_posed_images(...): every
     view is rendered at its pose (views sharded over the ranks like DDP's DistributedSampler), ALL views are aligned to
     their targets by ONE affine fit in log space per channel (:634-677: the reference flattens batch x H x W before its
     lstsq) -- each rank adds the normal-equation sums of its views, a 5C-double all-reduce replaces the image gather (C3)
-    -- and every view is then scored with L1 / PSNR over the target's pixel-value range (loss_metric/metric.py:60-72).
+    -- and every view is then scored with L1 / PSNR over the target's pixel-value range and SSIM with the target's largest
+    pixel value as data range (loss_metric/metric.py:60-81).
     The wrap-around duplicates DistributedSampler pads with are left out of the fit and of the means (a deviation from the
     reference under data parallelism when n_views % world != 0: its all-gather keeps them in both; documented, README).
-    -> dict(l1, psnr: means over the views; per_view: (V, 2) tensor; scale, offset: the fit)"""
+    ``save_dir``: each rank writes the aligned prediction of every view it owns as <save_dir>/<sample_id>.png (:736-780).
+    -> dict(l1, psnr, ssim: means over the views; per_view: (V, 2) tensor [l1, psnr]; per_view_ssim: (V,) float64;
+    scale, offset: the fit)"""
     dev = r.field.flat.device
     n = len(posed["sample_id"]) if limit is None else min(limit, len(posed["sample_id"]))
     if n == 0:                                             # no view at all (limit 0): nothing to fit (0 / 0 otherwise), nothing to score
-        return dict(l1=float("nan"), psnr=float("nan"), per_view=torch.zeros(0, 2), n_views=0, scale=None, offset=None)
+        return dict(l1=float("nan"), psnr=float("nan"), ssim=float("nan"), per_view=torch.zeros(0, 2),
+                    per_view_ssim=torch.zeros(0, dtype=torch.float64), n_views=0, scale=None, offset=None)
     Kinv = torch.linalg.inv(posed["intrinsics"].double()).float().contiguous().to(dev).contiguous()
     H, W = posed["img"].shape[-2:]
-    rng = posed["max_normalized_pixel_value"] - posed["min_normalized_pixel_value"]
+    lo, hi = posed["min_normalized_pixel_value"], posed["max_normalized_pixel_value"]
+    rng = hi - lo
     mine = view_shard(n, rank, world)
     fresh = [j * world + rank < n for j in range(len(mine))]          # False: a padded repeat of some other rank's view
     C = 1 if posed["img"].dim() == 3 else posed["img"].shape[1]
@@ -229,13 +267,24 @@ def evaluate_posed_images(r: Renderer, posed: dict, bkgd: Optional[torch.Tensor]
     if world > 1:
         import torch.distributed as dist
         dist.all_reduce(sums, group=group)
-    local = torch.zeros(len(mine), 2, device=dev)
+    # [l1, psnr] rounded to float32 as before (per_view keeps its values and dtype) | ssim in float64: one gather
+    local = torch.zeros(len(mine), 3, dtype=torch.float64, device=dev)
     a = b = None
     if mine:
         sc, (a, b) = align_and_score(torch.stack(preds), torch.stack(tgts), rng, sums)
-        local.copy_(sc)
+        local[:, :2].copy_(sc.to(torch.float32))
+        aligned = torch.stack([apply_affine(p_, a, b) for p_ in preds])
+        local[:, 2].copy_(ssim(aligned, torch.stack(tgts).float(), hi, batched=True))
+        if save_dir is not None:
+            import os
+            os.makedirs(save_dir, exist_ok=True)
+            for j, v in enumerate(mine):
+                if fresh[j]:
+                    save_prediction(aligned[j], lo, hi, os.path.join(save_dir, f"{posed['sample_id'][v]}.png"))
     else:
         a, b = solve_affine(sums)
-    per_view = gather_views(local, n, rank, world, group)
-    return dict(l1=float(per_view[:, 0].mean()), psnr=float(per_view[:, 1].mean()), per_view=per_view.cpu(), n_views=n,
-                scale=a.cpu(), offset=b.cpu())
+    gathered = gather_views(local, n, rank, world, group)
+    per_view = gathered[:, :2].to(torch.float32)
+    per_view_ssim = gathered[:, 2].cpu()
+    return dict(l1=float(per_view[:, 0].mean()), psnr=float(per_view[:, 1].mean()), ssim=float(per_view_ssim.mean()),
+                per_view=per_view.cpu(), per_view_ssim=per_view_ssim, n_views=n, scale=a.cpu(), offset=b.cpu())

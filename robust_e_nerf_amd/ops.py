@@ -629,6 +629,25 @@ def column_sum(x: torch.Tensor):
     return out
 
 
+# ------------------------------------------------------------------------------- evaluation metrics
+def ssim_scratch_doubles(P: int, H: int, W: int) -> int:
+    return int(_lib.load().ren_ssim_scratch_doubles(P, H, W))
+
+
+def ssim_planes(pred: torch.Tensor, target: torch.Tensor, data_range: float) -> torch.Tensor:
+    """(P, H, W) float32 device tensors -> (P,) float64: the mean SSIM of every plane over its (H - 10) x (W - 10) valid
+    windows (torchmetrics ssim with the reference's arguments, loss_metric/metric.py:74-81), one launch for all planes"""
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise ValueError(f"ssim_planes takes two (P, H, W) tensors of one shape; got {tuple(pred.shape)}, {tuple(target.shape)}")
+    pred, target = pred.contiguous(), target.contiguous()
+    P, H, W = pred.shape
+    out = torch.empty(P, device=pred.device, dtype=torch.float64)
+    scratch = torch.empty(max(1, ssim_scratch_doubles(P, H, W)), device=pred.device, dtype=torch.float64)
+    check(_lib.load().ren_ssim_planes(_ptr(pred, torch.float32), _ptr(target, torch.float32), P, H, W, float(data_range),
+                                      _ptr(out), _ptr(scratch), _stream()), "ren_ssim_planes")
+    return out
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN = {"l1": 0, "mse": 1, "mape": 2}
 

@@ -4,12 +4,16 @@ reference (same state-dict keys).
 
     python scripts/render.py --config <YAML> --ckpt runs/train/last.ckpt --out renders/ \
         [--dataset-dir DIR | --synthetic] [--every 50] [--height 260 --width 346] [--gt-dir DIR]
+    python scripts/render.py --config <test YAML> --stage test --out renders/      # --ckpt: model.checkpoint_filepath
 
 Poses come from the dataset's camera_poses.npz (every `--every`-th pose) or from the synthetic benchmark orbit; the
 intrinsics from camera_calibration.npz.  Each view is written as <index>.png (8-bit, intensity clipped to [0, 1] after an
 optional gain) and all of them as views.npz (float32 intensity, opacity, z-depth).  With --gt-dir (files <index>.npy:
 linear intensity images of the same size) the prediction is aligned to the ground truth by the reference's affine fit in
-log space and the PSNR of every view and their mean are printed (metric.py:60-72).
+log space and the PSNR of every view and their mean are printed (metric.py:60-72).  With --stage val | test the
+dataset's posed views are scored as the reference's validation / test epochs score them: aligned L1, PSNR and SSIM per
+view and their means (metric.py:54-81), and with model.eval_save_pred_intensity_img the aligned predictions are written
+to <out>/predictions/<sample_id>.png (robust_e_nerf.py:736-780).
 """
 import argparse
 import math
@@ -25,10 +29,23 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "scripts"))
 
 
+def load_config(config: str, ckpt=None):
+    """the YAML, checked against what the kernels implement (train.check_supported), and the checkpoint to load: --ckpt, or
+    model.checkpoint_filepath as the reference's test YAMLs give it (configs/test/*.yaml)"""
+    import train as cli
+    cfg = yaml.safe_load(open(config))
+    ncfg = cfg["model"]["nerf"]
+    cli.check_supported(ncfg, ncfg.get("arch", "ngp"))
+    ckpt = ckpt or cfg["model"].get("checkpoint_filepath")
+    if not ckpt:
+        raise SystemExit(f"{config}: no checkpoint: pass --ckpt or set model.checkpoint_filepath")
+    return cfg, ckpt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
-    ap.add_argument("--ckpt", required=True)
+    ap.add_argument("--ckpt", help="checkpoint to render (default: the YAML's model.checkpoint_filepath)")
     ap.add_argument("--out", default="renders")
     ap.add_argument("--dataset-dir")
     ap.add_argument("--synthetic", action="store_true", help="poses / intrinsics of the synthetic benchmark orbit")
@@ -39,14 +56,14 @@ def main():
     ap.add_argument("--gt-dir", help="<index>.npy ground-truth intensity images: aligned PSNR is reported")
     ap.add_argument("--stage", choices=["val", "test"],
                     help="evaluate on the dataset's posed images (views/transforms_<stage>.json, the reference's PosedImage "
-                         "layout) instead of rendering along the trajectory: aligned L1 / PSNR per view and their means, as "
+                         "layout) instead of rendering along the trajectory: aligned L1 / PSNR / SSIM per view and their means, as "
                          "the reference's validation / test epochs (robust_e_nerf.py:519-696)")
     ap.add_argument("--chunk", type=int, help="rays per render call (default: whole image for arch ngp, 16 384 for arch mlp)")
     args = ap.parse_args()
 
     import train as cli
     from robust_e_nerf_amd import data, engine, evaluation, ops
-    cfg = yaml.safe_load(open(args.config))
+    cfg, ckpt = load_config(args.config, args.ckpt)
     dev = "cuda:0"
     torch.cuda.set_device(0)
     dcfg, mcfg, ncfg = cfg["data"], cfg["model"], cfg["model"]["nerf"]
@@ -75,10 +92,9 @@ def main():
                             alpha_thre=float(ncfg["alpha_thre"]), min_modeled_intensity=float(mcfg["min_modeled_intensity"]),
                             mlp_precision=cfg.get("float32_matmul_precision", "highest"))
     arch = ncfg.get("arch", "ngp")
-    cli.check_supported(ncfg, arch)
     for k_, v_ in cli.activation_fields(ncfg, arch).items():
         setattr(rcfg, k_, v_)
-    sd = torch.load(args.ckpt, map_location="cpu", weights_only=False)["state_dict"]
+    sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
     C = int(sd[cli.PREFIX + ("mlp.rgb_layer.output_layer.bias" if arch == "mlp" else cli.NGP_KEYS["head.bo"])].numel())
     if arch == "mlp":
         from robust_e_nerf_amd import vanilla
@@ -99,12 +115,14 @@ def main():
         if args.synthetic:
             raise SystemExit("--stage needs a dataset directory with a views/ folder")
         posed = data.load_eval_views(root, args.stage, dcfg, cfg.get("eval_target"))      # datamodule.py:100-134
-        m = evaluation.evaluate_posed_images(r, posed, bkgd, chunk=args.chunk)
-        for sid, (l1v, ps) in zip(posed["sample_id"], m["per_view"].tolist()):
-            print(f"{args.stage} view {sid}: l1 {l1v:.5f}  psnr {ps:.2f} dB")
+        save = os.path.join(args.out, "predictions") if mcfg.get("eval_save_pred_intensity_img") else None
+        m = evaluation.evaluate_posed_images(r, posed, bkgd, chunk=args.chunk, save_dir=save)
+        for sid, (l1v, ps), ss in zip(posed["sample_id"], m["per_view"].tolist(), m["per_view_ssim"].tolist()):
+            print(f"{args.stage} view {sid}: l1 {l1v:.5f}  psnr {ps:.2f} dB  ssim {ss:.4f}")
         np.savez(os.path.join(args.out, f"{args.stage}_metrics.npz"), sample_id=np.array(posed["sample_id"]),
-                 l1_psnr=m["per_view"].numpy())
-        print(f"{args.stage}: {m['n_views']} views, mean l1 {m['l1']:.5f}, mean PSNR {m['psnr']:.2f} dB", flush=True)
+                 l1_psnr=m["per_view"].numpy(), ssim=m["per_view_ssim"].numpy())
+        print(f"{args.stage}: {m['n_views']} views, mean l1 {m['l1']:.5f}, mean PSNR {m['psnr']:.2f} dB, "
+              f"mean SSIM {m['ssim']:.4f}", flush=True)
         return
     Kinv_d = Kinv.to(dev, torch.float32)
     idx = list(range(0, tab_ts.shape[0], max(1, args.every)))

@@ -363,9 +363,13 @@ def main():
         if val_views is not None and (epoch + 1) % val_every == 0:
             from robust_e_nerf_amd import evaluation
             bk = torch.nn.functional.softplus(tr.small[: fld.C]) if tcfg.bkgd_is_param else None
-            vm = evaluation.evaluate_posed_images(renderer, val_views, bk, rank, world, limit=args.limit_val_batches)
+            # model.eval_save_pred_intensity_img: the aligned predictions in <out>/predictions/, overwritten every epoch (:736-780)
+            save = os.path.join(args.out, "predictions") if mcfg.get("eval_save_pred_intensity_img") else None
+            vm = evaluation.evaluate_posed_images(renderer, val_views, bk, rank, world, limit=args.limit_val_batches,
+                                                  save_dir=save)
             if rank == 0:
-                print(f"epoch {epoch} validation over {vm['n_views']} views: val/l1 {vm['l1']:.5f}  val/psnr {vm['psnr']:.3f} dB", flush=True)
+                print(f"epoch {epoch} validation over {vm['n_views']} views: val/l1 {vm['l1']:.5f}  val/psnr {vm['psnr']:.3f} dB"
+                      f"  val/ssim {vm['ssim']:.4f}", flush=True)
         mine_rng = {"batcher": batcher.gen.get_state().cpu(), "jitter": jgen.get_state().cpu()}
         rank_rng = [mine_rng]
         if world > 1:                                           # every rank's generator states travel to rank 0's file

@@ -21,6 +21,7 @@ import threading
 import torch
 
 from . import ops
+from .step_graph import StepGraphs
 
 
 @dataclass
@@ -239,7 +240,7 @@ class CountLog:
     """The two sample counts of one render sampled with device-side counts -- marched, kept -- and whether they fitted the
     capacities the arrays were given: copied to pinned memory behind the sampling kernels.  wait() blocks the host until
     THOSE kernels are done (an event), not until the queue is empty.
-    polled=True (a render inside a captured step, Trainer._graph_step): the copy is a node of the graph and no event can be
+    polled=True (a render inside a captured step, step_graph.StepGraphs): the copy is a node of the graph and no event can be
     waited for; the host arms the pinned words with -1 before every replay (arm()) and wait() spins until the copy has
     landed -- pinned host memory is coherent, and each of the four words is one aligned 8-byte store."""
 
@@ -330,8 +331,7 @@ class Renderer:
         # learnt from the renders themselves -- the first one reads its counts on the host -- and a ring of pinned buffers
         self._spr = None
         self._count_ring, self._count_ring_at = None, 0
-        self._polled_logs = None                    # a list while a step is being captured (Trainer._capture): its renders' CountLogs
-        self._polled_pinned = None                  # ... and the pinned words allocated for them before the capture began
+        self._capture = None                        # step_graph.Capture while a step is being captured
         self.dp_early_enabled = True                # the Trainer clears it when a loss pass may have to be repeated (device-side counts)
         self.bwd_side_cus = 0                       # CUs the persistent MLP backward kernels leave free (Trainer: a side stream is at work)
         self._act_code = ops.activation_code(cfg.base_hidden_activation, cfg.density_activation, cfg.head_hidden_activation,
@@ -444,10 +444,8 @@ class Renderer:
         self._spr = m if self._spr is None else tuple(max(a, 0.75 * b + 0.25 * a) for a, b in zip(m, self._spr))
 
     def _count_log(self, n_rays: int, caps, stats: torch.Tensor) -> CountLog:
-        if self._polled_logs is not None:                        # inside a capture: the graph owns its pinned words
-            log = CountLog(n_rays, caps, stats, self._polled_pinned.pop(), polled=True)   # (pinned before the capture began)
-            self._polled_logs.append(log)
-            return log
+        if self._capture is not None:                            # inside a capture: the graph owns its pinned words
+            return CountLog(n_rays, caps, stats, self._capture.pinned.pop(), polled=True)   # (pinned before the capture began)
         if self._count_ring is None:
             self._count_ring = [torch.empty(4, dtype=torch.int64).pin_memory() for _ in range(16)]
             self._count_logs = [None] * 16
@@ -544,10 +542,11 @@ class Renderer:
     def _binned_workspace(self, n: int, device) -> torch.Tensor:
         """staging pool of the binned hash-grid backward (~1.4 KB per sample): grown on demand, and given back when a pass
         needs less than a quarter of it for 32 passes in a row -- the first steps of a run, before the occupancy grid has
-        pruned and the batch size has adapted, can march 50 M samples (an 80 GB pool that would otherwise stay)"""
+        pruned and the batch size has adapted, can march 50 M samples (an 80 GB pool that would otherwise stay).  A captured
+        step holds its pool: one given back here is freed at the next StepGraphs.find, which drops such steps, not at once"""
         need = ops.hashgrid_bwd_binned_workspace_bytes(n)
         ws = self._bin_ws
-        if self._polled_logs is not None:                             # inside a capture: the pool was sized before it began
+        if self._capture is not None:                                 # inside a capture: the pool was sized before it began
             if ws is None or ws.numel() < need:
                 raise RuntimeError("binned-scatter workspace too small for the step being captured")
             return ws
@@ -941,13 +940,11 @@ class Trainer:
         self._dc_sync, self.device_count_overflows = False, 0
         self.keep_ctx = False                                    # tests: aux["ctx"] = the render's context (rays, samples, features)
         # optimiser state on the device (ABI 25, ops.HY_*): Adam step numbers and bias corrections, and the sticky skip word a
-        # captured step raises when one of its device-side counts did not fit (Trainer._graph_step)
+        # captured step raises when one of its device-side counts did not fit (step_graph.StepGraphs)
         self._hyper = torch.zeros(8, dtype=torch.float64, device=dev)
-        self.use_graph: Optional[bool] = None                    # Trainer.step: None = auto (a step shape seen twice in a row), False = never
-        if os.environ.get("REN_STEP_GRAPH", "") in ("0", "off"):
-            self.use_graph = False
-        self._graphs, self._graph_last_key, self._graph_pool, self._capturing, self._graph_streak = {}, None, None, False, 0
-        self._graph_bad, self._graph_eager_ev = {}, None         # per step shape: captures that replayed no faster than eager steps
+        # Trainer.step: None = auto (a step shape seen three times in a row), False = never (REN_STEP_GRAPH=0|off)
+        self.use_graph: Optional[bool] = False if os.environ.get("REN_STEP_GRAPH", "") in ("0", "off") else None
+        self.step_graphs = StepGraphs()
         self.graph_replays = self.graph_captures = 0
         self.lr_scale = 1.0
         # trainable C_p / C_n ratio (softplus-parametrised scalar, its own Adam group with lr 0.1:
@@ -1015,35 +1012,46 @@ class Trainer:
 
     def _dc_pass(self, fn, args):
         """Run one loss pass (`fn(*args, dc)` -> loss, aux, CountLog | None) with its sample counts on the device, then look
-        at them: a wait for the pass's SAMPLING kernels -- its field evaluation and backward are still in the queue.  A count
-        that did not fit its arrays left the render empty: the table / MLP gradients got nothing from it, the scalar
-        parameters' gradient block is put back, and the pass runs again with host-side counts."""
-        dc = self._dc_mode()
-        if self._capturing:                                  # _graph_step looks at the counts after every replay
-            loss, aux, log = fn(*args, dc)
+        at them (_settle; its field evaluation and backward are still in the queue).  A count that did not fit its arrays left
+        the render empty: the scalar parameters' gradient block is put back and the pass runs again with host-side counts."""
+        dc, cap = self._dc_mode(), self.r._capture
+        snap = self._gs.clone() if dc is True and cap is None else None
+        loss, aux, log = fn(*args, dc)
+        if cap is not None:                                  # StepGraphs looks at the counts after every replay
             if log is None:
                 raise RuntimeError("a captured step needs every render on device-side counts")
-            self._cap_passes.append((log, aux))
-            return loss, aux
-        snap = self._gs.clone() if dc is True else None
-        loss, aux, log = fn(*args, dc)
-        if log is None:
-            return loss, aux
-        v = log.wait()
-        if not (v[1] or v[3]):
+            cap.passes.append((log, aux))
+        elif log is not None and self._settle([(log, aux)]):
+            self._gs.copy_(snap)         # (not _clear_grads: this pass added nothing to the table / MLP gradients, earlier ones did)
+            loss, aux, _ = self._repeat_with_host_counts(lambda: fn(*args, self._dc_mode()))
+        return loss, aux
+
+    def _settle(self, passes) -> bool:
+        """wait for the counts of loss passes [(CountLog, aux), ...] -> whether one did not fit; else the capacities and auxes get them"""
+        vals = [log.wait() for log, _ in passes]
+        if any(v[1] or v[3] for v in vals):
+            return True
+        for (log, aux), v in zip(passes, vals):
             self.r._learn_counts(log.n_rays, v[0], v[2])
             aux["n"] = v[2]
             if "n_marched" in aux:
                 aux["n_marched"] = v[0]
-            return loss, aux
-        self._gs.copy_(snap)
+        return False
+
+    def _repeat_with_host_counts(self, fn):
+        """fn() again with host-side counts (the capacities learn from them), after a device-side count did not fit"""
         self.device_count_overflows += 1
         self._dc_sync, self._grad_begun, self._grad_pending = True, None, None
         try:
-            loss, aux, _ = fn(*args, self._dc_mode())
+            return fn()
         finally:
             self._dc_sync = False
-        return loss, aux
+
+    def _clear_grads(self):
+        self.r.field.grad_all.zero_()
+        if getattr(self.r.field, "n_wn_g", 0):
+            self.r.field.g_mlp.zero_()
+        self._gs.zero_()
 
     @property
     def tau_grad(self) -> torch.Tensor:
@@ -1448,11 +1456,11 @@ class Trainer:
         gs = 1.0 / (self.world_size * accumulate_grad_batches)            # mean over ranks and accumulated micro-batches
         lr = self.t.lr * self.lr_scale
         # step numbers / bias corrections live on the device (ops.HY_*): the same launches serve the eager step and a captured
-        # one, whose renders' overflow words raise the skip word instead (Trainer._graph_step)
+        # one, whose renders' overflow words raise the skip word instead (step_graph.StepGraphs)
         hy = self._hyper
         if self.t.train_refractory_period:
             self._tau_adam_steps += 1
-        stats = [log.stats for log in self.r._polled_logs] if self._capturing else []
+        stats = [log.stats for log, _ in self.r._capture.passes] if self.r._capture is not None else []
         ops.step_tick(hy, self.t.betas, stats=stats, tick_tau=self.t.train_refractory_period)
         ops.adam_step_dev(f.flat, f.grad, self.m, self.v, hy, lr=lr, betas=self.t.betas, eps=self.t.eps,
                           weight_decay=self.t.weight_decay, grad_scale=gs, zero_grad=True)
@@ -1549,13 +1557,13 @@ class Trainer:
         refreshed on the first micro-batch only (robust_e_nerf.py:375-379), gradients add up over the micro-batches
         and the optimiser steps on the last one with their mean.
         A step whose shape (event count, capacities of its renders, learning-rate factor) repeats is captured in a hipGraph
-        and replayed as ONE launch from then on (`use_graph`, _graph_step)."""
+        and replayed as ONE launch from then on (`use_graph`, step_graph.StepGraphs)."""
         k = max(1, accumulate_grad_batches)
         bi = 0 if batch_index is None else batch_index
         if global_step is not None and bi % k == 0:
             self.r.update_occ_grid(global_step, self.tab_pos)
         if k == 1:
-            out = self._graph_step(batch, jitter_start, jitter_end, jitter_grad)
+            out = self.step_graphs.step(self, batch, jitter_start, jitter_end, jitter_grad)
             if out is not None:
                 return out
         return self._step_passes(batch, jitter_start, jitter_end, jitter_grad, bi, k)
@@ -1580,7 +1588,7 @@ class Trainer:
         if self.t.w_grad > 0:
             lg, aux_g = self.grad_loss_forward_backward(batch, jitter_grad, final=last, early=mode != "inorder")
             loss = loss + lg
-            aux = dict(aux, grad=aux_g)
+            aux["grad"] = aux_g
         if (bi + 1) % k == 0 and optimizer:
             self._optimizer_after_passes(aux, k)
         return loss, aux
@@ -1593,214 +1601,10 @@ class Trainer:
         self.optimizer_step(k, mean_samples_per_ray=mean)
         aux["_mean_s_synced"] = self.world_size > 1
 
-    # ---- the whole step as one hipGraph launch (the reference's step shape: models/robust_e_nerf.py:301-517) ----
-    GRAPH_CACHE = 8
-
-    def _graph_key(self, batch, jitter_start, jitter_end, jitter_grad):
-        """what a captured step is specialised to -- or None when this step cannot be captured: device-side counts with known
-        capacities for every render (occupancy sampler, one GPU), no gradient accumulation.  The capacities in the key are
-        those of a cached graph of the same shape that still fits the learnt counts with a margin (capturing costs ~10 steps:
-        a graph is kept while the counts drift by a few per cent), otherwise what Renderer._capacities gives now."""
-        r, t = self.r, self.t
-        if self.use_graph is False or not r.field.flat.is_cuda or not self.device_counts_ok() or \
-                r._spr is None or self._dc_sync or (jitter_end is not None and jitter_start is None):
-            return None
-        B = batch["position"].shape[0]
-        rays = [2 * B] + ([B] if t.w_grad > 0 else [])
-        caps = [r._capacities(n) for n in rays]
-        if any(c is None for c in caps):
-            return None
-        sig = tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in batch.items() if isinstance(v, torch.Tensor)))
-        shape = (B, float(self.lr_scale), self.grad_sampling_mode(), jitter_start is not None, jitter_grad is not None, sig,
-                 t.train_contrast_threshold, t.train_refractory_period, float(t.w_grad))
-        need = [tuple(int(n * s * 1.08) + 1024 for s in r._spr) for n in rays]
-        for key in self._graphs:
-            if key[1:] == shape and all(c >= m and c <= 3 * m + 16384 for kc, km in zip(key[0], need) for c, m in zip(kc, km)):
-                return key
-        return (tuple(caps),) + shape
-
-    def _graph_step(self, batch, jitter_start, jitter_end, jitter_grad):
-        """replay (or capture, the second time a step shape occurs in a row) -> (loss, aux), or None: run the step eagerly"""
-        key = self._graph_key(batch, jitter_start, jitter_end, jitter_grad)
-        if key is None:
-            self._graph_last_key = None
-            return None
-        sg = self._graphs.get(key)
-        if sg is not None and sg["ws_ptr"] != (self.r._bin_ws.data_ptr() if self.r._bin_ws is not None else 0):
-            # the staging pool of the binned scatter was reallocated since this graph was captured (an eager step in between
-            # needed more, or handed it back): its launches carry the old address
-            self._graphs.pop(key)
-            sg = None
-        if sg is None:
-            if self.use_graph is None:                   # auto: a shape has to keep repeating before it is worth a capture
-                if self._graph_bad.get(key[1:], 0) >= 3:
-                    return None                          # (captured three times, never replayed faster than the eager step: stays eager)
-                # (the SHAPE has to repeat -- event count, flags, lr factor; the capacities in the key follow the counts)
-                self._graph_streak = self._graph_streak + 1 if (self._graph_last_key or (None,))[1:] == key[1:] else 0
-                self._graph_last_key = key               # (the reference's dynamic batch size changes the event count nearly
-                if self._graph_streak < 2:               # every step: such a run never captures -- scripts/train.py --batch-size-quantum)
-                    # the eager steps in front of a capture are timed: a graph has to beat them to be kept (_capture)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    out = self._step_passes(batch, jitter_start, jitter_end, jitter_grad, optimizer=self.world_size == 1)
-                    e1.record()                          # (what the graph will contain: under data parallelism the passes only)
-                    self._graph_eager_ev = (key[1:], e0, e1)
-                    if self.world_size > 1:
-                        self._optimizer_after_passes(out[1])
-                    return out
-            sg = self._capture(key, batch, jitter_start if jitter_end is None else torch.cat([jitter_start, jitter_end]),
-                               jitter_grad)
-            if sg is None:
-                return None
-        self._graph_last_key = key
-        # inputs -> the graph's static buffers (skipped for a tensor that already IS the static buffer: graph_inputs())
-        if "_pack" in batch and "_pack" in sg["batch"] and batch["_pack"].numel() == sg["batch"]["_pack"].numel():
-            if batch["_pack"].data_ptr() != sg["batch"]["_pack"].data_ptr():
-                sg["batch"]["_pack"].copy_(batch["_pack"], non_blocking=True)      # (engine.pack_batch: one launch for all fields)
-        else:
-            for k, dst in sg["batch"].items():
-                if k != "_pack" and batch[k].data_ptr() != dst.data_ptr():
-                    dst.copy_(batch[k], non_blocking=True)
-        B = batch["position"].shape[0]
-        parts = [(sg["j0"], jitter_start), (sg["j2"], jitter_grad)] if jitter_end is None else \
-            [(sg["j0"][:B], jitter_start), (sg["j0"][B:], jitter_end), (sg["j2"], jitter_grad)]
-        for dst, src in parts:
-            if dst is not None and src.data_ptr() != dst.data_ptr():
-                dst.copy_(src, non_blocking=True)
-        for log, _ in sg["passes"]:
-            log.arm()
-        sg["graph"].replay()
-        self.graph_replays += 1
-        self._ep_stale = True
-        # the counts of this step's renders: a wait for its SAMPLING kernels (pinned words), the rest is still in flight
-        over = False
-        for log, _ in sg["passes"]:
-            v = log.wait()
-            over = over or bool(v[1] or v[3])
-        if not over:
-            for i, (log, aux) in enumerate(sg["passes"]):
-                v = log.values
-                self.r._learn_counts(log.n_rays, v[0], v[2])
-                for a in ((aux, sg["aux"]) if i == 0 else (aux,)):      # (the step's aux is a copy of the first pass's dict)
-                    a["n"] = v[2]
-                    if "n_marched" in a:
-                        a["n_marched"] = v[0]
-            if self.world_size > 1:
-                # data parallelism: the graph ends where the gradient exchange begins -- all-reduce and optimiser launches
-                # are enqueued from here while the graph's backward is still running (they count the step themselves)
-                self._optimizer_after_passes(sg["aux"])
-                return sg["loss"], sg["aux"]
-            self.step_count += 1
-            if self.t.train_refractory_period:
-                self._tau_adam_steps += 1
-            return sg["loss"], sg["aux"]
-        # a count did not fit: the graph's optimiser launches saw the skip word and changed nothing.  Clear what its passes
-        # left in the gradient buffers and run the step again with host-side counts (the capacities learn from them).
-        # (data parallelism: THIS rank repeats its passes by itself, before the collective that its peers are waiting in)
-        f = self.r.field
-        f.grad_all.zero_()
-        if getattr(f, "n_wn_g", 0):
-            f.g_mlp.zero_()
-        self._gs.zero_()
-        if self.world_size == 1:
-            self._sync_hyper()
-        self.device_count_overflows += 1
-        self._dc_sync, self._grad_begun, self._grad_pending = True, None, None
-        try:
-            return self._step_passes(batch, jitter_start, jitter_end, jitter_grad)
-        finally:
-            self._dc_sync = False
-
     def graph_inputs(self, batch, jitter_start=None, jitter_grad=None):
-        """the static input buffers of the captured step this call would replay -> (batch dict, jitter_start, jitter_grad) to
-        write the NEXT step's inputs into directly (then step() copies nothing), or None when there is no such graph yet"""
-        key = self._graph_key(batch, jitter_start, None, jitter_grad)
-        sg = self._graphs.get(key) if key is not None else None
-        return None if sg is None else (sg["batch"], sg["j0"], sg["j2"])
+        """the static inputs (batch dict, jitter_start, jitter_grad) of the captured step this call would replay, or None"""
+        rec = self.step_graphs.find(self, batch, jitter_start, None, jitter_grad)[1]
+        return None if rec is None else (rec.batch, rec.j0, rec.j2)
 
-    def _capture(self, key, batch, jitter_start, jitter_grad):
-        r = self.r
-        dev = r.field.flat.device
-        if len(self._graphs) >= self.GRAPH_CACHE:            # oldest out (its memory stays in the shared pool for the others)
-            self._graphs.pop(next(iter(self._graphs)))
-        st_batch = pack_batch(batch) if "_pack" in batch else {k: v.clone() for k, v in batch.items() if isinstance(v, torch.Tensor)}
-        j0 = jitter_start.to(torch.float32).clone() if jitter_start is not None else None
-        j2 = jitter_grad.to(torch.float32).clone() if jitter_grad is not None else None
-        caps = key[0]
-        if r.cfg.binned_scatter:
-            # sized before the capture (nothing (re)allocates inside) and with room to spare: a larger step shape later on
-            # then finds it big enough, and the graphs captured so far stay valid (they carry its address)
-            need = max(max(c) for c in caps)
-            if r._bin_ws is None or r._bin_ws.numel() < ops.hashgrid_bwd_binned_workspace_bytes(need):
-                r._binned_workspace(2 * need, dev)
-        _ = self.side_stream
-        pinned = [torch.empty(4, dtype=torch.int64).pin_memory() for _ in range(len(caps))]
-        # (a pool lives as long as a graph that was captured into it: with the last one gone the handle is dead -- torch asserts on
-        # a capture into it -- so an empty cache starts a new pool)
-        if self._graph_pool is None or not self._graphs or os.environ.get("REN_STEP_GRAPH_POOL") == "own":
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        dump = os.environ.get("REN_STEP_GRAPH_DUMP")             # debugging: <prefix><capture number>.dot of every captured step
-        if dump:
-            g.enable_debug_mode()
-        host_state = (self.step_count, self._tau_adam_steps, self._ep_stale)
-        r._polled_logs, r._polled_pinned, self._cap_passes, self._capturing = [], pinned, [], True
-        self._grad_begun, self._grad_pending = None, None
-        ok = False
-        try:
-            with torch.cuda.graph(g, pool=self._graph_pool):
-                loss, aux = self._step_passes(st_batch, j0, None, j2, optimizer=self.world_size == 1)
-            ok = True
-        except Exception as e:                               # a capture that cannot be made is not an error of the step
-            import warnings
-            warnings.warn(f"step capture failed ({type(e).__name__}: {e}); this trainer runs eagerly from here on")
-            self.use_graph = False
-        finally:
-            passes = self._cap_passes
-            r._polled_logs, r._polled_pinned, self._cap_passes, self._capturing = None, None, None, False
-            self.step_count, self._tau_adam_steps, self._ep_stale = host_state       # (nothing ran)
-            self._grad_begun, self._grad_pending = None, None
-        if not ok:
-            return None
-        self.graph_captures += 1
-        if dump:
-            g.debug_dump(f"{dump}{self.graph_captures}.dot")
-        sg = dict(graph=g, batch=st_batch, j0=j0, j2=j2, loss=loss, aux=aux, passes=passes,
-                  ws_ptr=r._bin_ws.data_ptr() if r._bin_ws is not None else 0)
-        # Does the replay beat the eager step?  A captured step with a forked branch (the third render's sampling) replays
-        # through a second hardware queue, and on this runtime WHICH queue the graph's internal stream lands on decides
-        # whether the replay is faster than the eager launches or 25 % slower (tools/recapture_probe.py: every other capture
-        # of the same step; a single-stream graph is slower still at a few million samples).  So a capture is measured before
-        # it is used: three replays with the optimiser's skip word raised (parameters and moments untouched, the gradient
-        # buffers cleared afterwards) against the eager steps that ran just before it.
-        ev = self._graph_eager_ev
-        if self.use_graph is None and ev is not None and ev[0] == key[1:]:
-            t_eager = ev[1].elapsed_time(ev[2])
-            t_graph = self._time_skip_replays(sg)
-            sg["ms"] = (t_graph, t_eager)
-            if t_graph > 0.97 * t_eager:
-                self._graph_bad[key[1:]] = self._graph_bad.get(key[1:], 0) + 1
-                self._graph_streak = 1                       # (the next step tries again: up to three attempts per shape)
-                return None
-        self._graphs[key] = sg
-        return sg
-
-    def _time_skip_replays(self, sg, reps: int = 3) -> float:
-        """ms per replay of a captured step that changes nothing: skip word raised, gradients cleared afterwards"""
-        f = self.r.field
-        self._hyper[ops.HY_SKIP: ops.HY_SKIP + 1].fill_(1.0)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sg["graph"].replay()                                 # (first replay of a fresh executable: not timed)
-        e0.record()
-        for _ in range(reps):
-            sg["graph"].replay()
-        e1.record()
-        f.grad_all.zero_()
-        if getattr(f, "n_wn_g", 0):
-            f.g_mlp.zero_()
-        self._gs.zero_()
-        self._sync_hyper()
-        if self.t.train_refractory_period or self.t.train_contrast_threshold:
-            self._refresh_event_params()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps
+    _graphs = property(lambda self: self.step_graphs.cache)          # (bench.py and the tests read these two)
+    _graph_bad = property(lambda self: self.step_graphs.bad)

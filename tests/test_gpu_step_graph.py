@@ -1,14 +1,17 @@
-"""The training step as ONE hipGraph launch (Trainer._graph_step).  A step whose shape repeats -- event
+"""The training step as ONE hipGraph launch (step_graph.StepGraphs).  A step whose shape repeats -- event
 count, capacities of its renders' device-side sample counts, learning-rate factor -- is captured once and replayed: the same
 launches in the same order, so the same sample counts, losses and parameters as the eager step, step after step; the
 optimiser's step numbers live on the device (ren_step_tick / ren_adam_step_dev, ABI 25), and a count that does not fit its
 arrays raises the skip word there: the captured optimiser launches then change nothing and the host repeats the step with
 host-side counts (the reference's own placement of the reads: external/utils.py:106-119, models/nerf.py:279-286)."""
+import weakref
+
 import numpy as np
 import pytest
 import torch
 
 from test_gpu_parity import DEV, _config_batch, _trainer_from_golden, amd, dev, load_golden      # noqa: F401  (amd: fixture)
+from conftest import elem_err, rel_err
 from test_gpu_device_counts import _same
 # (ptol = 1e-3 below: after a few Adam steps a parameter whose gradient is ~0 has moved by lr x g / (|g| + eps) = +-0.01 per step
 # whatever |g| is, so another summation order of the MLP weight gradients -- a replayed step, or `side_cus` CUs left free: another
@@ -18,7 +21,7 @@ from test_gpu_device_counts import _same
 pytestmark = pytest.mark.gpu
 
 
-def _run(engine, g, table, use_graph, steps=6, B=2048, w_grad=0.0, trainable=False, squeeze_at=None):
+def _run(engine, g, table, use_graph, steps=6, B=2048, w_grad=0.0, trainable=False, squeeze_at=None, before_step=None):
     tr, _ = _trainer_from_golden(engine, g, table)
     tr.use_graph = use_graph
     if w_grad:
@@ -34,6 +37,8 @@ def _run(engine, g, table, use_graph, steps=6, B=2048, w_grad=0.0, trainable=Fal
         j = [dev(torch.rand(B, generator=gen)) for _ in range(3)]
         if squeeze_at is not None and i == squeeze_at and tr.r._spr is not None:
             tr.r._spr = tuple(0.25 * s for s in tr.r._spr)          # arrays four times too small: both guards must trip
+        if before_step is not None:
+            before_step(tr, i)
         loss, aux = tr.step(batch, j[0], j[1], jitter_grad=j[2] if w_grad else None)
         rec = dict(loss=float(loss), n=int(aux["n"]), n_marched=int(aux["n_marched"]),
                    n_grad=int(aux["grad"]["n"]) if w_grad else 0, table=tr.r.field.table.clone(), mlp=tr.r.field.mlp.clone(),
@@ -89,6 +94,83 @@ def test_overflow_inside_a_replayed_step_is_repeated_exactly(amd, full_table_cac
     hy = tr._hyper.tolist()
     assert hy[ops.HY_STEP] == 6 and hy[ops.HY_SKIP] == 0.0
     _same(got, ref, ptol=1e-3)
+
+
+@pytest.mark.parametrize("trainable", [False, True], ids=["l_diff+l_grad", "C_p,tau"])
+def test_replayed_passes_give_the_eager_passes_gradients(amd, full_table_cache, trainable):
+    """what Adam does not amplify: one replay of a captured step with the optimiser's skip word raised (parameters, moments and
+    gradients then stay where its passes left them) against the same step's passes run eagerly from the same state, same inputs,
+    device-side counts -- the table / MLP gradients to 2e-5 of their largest entry, each scalar gradient to 2e-5"""
+    ops, engine = amd
+    g = load_golden("training_step_grad")
+    table = full_table_cache(g["table_seed"], g["table_scale"])
+    _, tr = _run(engine, g, table, True, steps=3, w_grad=1e-3, trainable=trainable)
+    replays = tr.graph_replays
+    assert replays >= 2 and tr.device_count_overflows == 0
+    rec = list(tr._graphs.values())[-1]
+    f = tr.r.field
+    grads = lambda: dict(grad_all=f.grad_all.clone(), small=tr.small_grad.clone(), ct=tr.ct_grad.clone(), tau=tr._tau_grad_dev.clone())
+    tr._clear_grads()
+    params = (f.flat.clone(), tr.m.clone(), tr.v.clone(), tr.small.clone(), tr.ct.clone(), tr._tau_raw_dev.clone())
+    tr._hyper[ops.HY_SKIP: ops.HY_SKIP + 1].fill_(1.0)
+    for log, _ in rec.passes:
+        log.arm()
+    rec.graph.replay()
+    assert not any(log.overflowed for log, _ in rec.passes)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(params, (f.flat, tr.m, tr.v, tr.small, tr.ct, tr._tau_raw_dev)))
+    got = grads()
+    tr._clear_grads()
+    tr._sync_hyper()                                     # (clears the skip word)
+    tr._step_passes(rec.batch, rec.j0, None, rec.j2, optimizer=False)
+    torch.cuda.synchronize()
+    assert tr.device_count_overflows == 0 and tr.graph_replays == replays
+    ref = grads()
+    assert float(ref["grad_all"].abs().max()) > 0 and float(ref["small"].abs().max()) > 0
+    errs = dict(grad_all=rel_err(got["grad_all"], ref["grad_all"]), bitwise=torch.equal(got["grad_all"], ref["grad_all"]),
+                **{k: elem_err(got[k], ref[k]) for k in ("small", "ct", "tau")})
+    print("replayed vs eager passes:", errs)
+    assert errs["grad_all"] <= 2e-5, errs
+    for k in ("small", "ct", "tau"):
+        assert errs[k] <= 2e-5, (k, errs)
+    if trainable:
+        assert float(ref["ct"].abs().max()) > 0 and float(ref["tau"].abs().max()) > 0
+
+
+class _Stale:
+    def replay(self):
+        raise AssertionError("a captured step whose staging pool was reallocated was replayed")
+
+
+def test_a_reallocated_workspace_forces_a_fresh_capture(amd, full_table_cache):
+    """a new binned-scatter staging pool of the same size (as a reallocation would leave, possibly at the same address): the next
+    step captures afresh and never replays a step captured with the old pool; the steps equal the eager run's"""
+    ops, engine = amd
+    g = load_golden("training_step_grad")
+    table = full_table_cache(g["table_seed"], g["table_scale"])
+    seen = {}
+
+    def swap(tr, i):
+        if i == 3:
+            assert tr.graph_replays >= 1 and tr.r._bin_ws is not None
+            seen.update(captures=tr.graph_captures, replays=tr.graph_replays, stale=len(tr._graphs))
+            for rec in tr._graphs.values():
+                rec.graph = _Stale()                         # (any replay of it fails the test)
+            tr.r._bin_ws = torch.empty_like(tr.r._bin_ws)
+        if i == 4:
+            assert tr.graph_captures == seen["captures"] + 1 and tr.graph_replays == seen["replays"] + 1, (seen, tr.graph_captures)
+        if i >= 4:
+            assert tr._graphs and all(rec.ws is tr.r._bin_ws for rec in tr._graphs.values())
+    ref, _ = _run(engine, g, table, False, w_grad=1e-3)
+    got, tr = _run(engine, g, table, True, w_grad=1e-3, before_step=swap)
+    assert seen["stale"] >= 1 and tr.device_count_overflows == 0 and tr.step_count == 6
+    assert all(rec.ws is tr.r._bin_ws for rec in tr._graphs.values())
+    _same(got, ref, ptol=1e-3)
+    # no reference cycle through the trainer: its graphs go with it, not later in Python's cycle collector -- which may run inside
+    # another capture, where destroying a graph aborts the process
+    alive = weakref.ref(tr)
+    del tr
+    assert alive() is None
 
 
 def test_device_side_optimiser_state_matches_the_host_side_calls(amd):

@@ -16,7 +16,6 @@ view and their means (metric.py:54-81), and with model.eval_save_pred_intensity_
 to <out>/predictions/<sample_id>.png (robust_e_nerf.py:736-780).
 """
 import argparse
-import math
 import os
 import sys
 
@@ -26,16 +25,15 @@ import yaml
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "scripts"))
 
 
 def load_config(config: str, ckpt=None):
-    """the YAML, checked against what the kernels implement (train.check_supported), and the checkpoint to load: --ckpt, or
+    """the YAML, checked against what the kernels implement (config.check_supported), and the checkpoint to load: --ckpt, or
     model.checkpoint_filepath as the reference's test YAMLs give it (configs/test/*.yaml)"""
-    import train as cli
+    from robust_e_nerf_amd import config as schema
     cfg = yaml.safe_load(open(config))
     ncfg = cfg["model"]["nerf"]
-    cli.check_supported(ncfg, ncfg.get("arch", "ngp"))
+    schema.check_supported(ncfg, ncfg.get("arch", "ngp"))
     ckpt = ckpt or cfg["model"].get("checkpoint_filepath")
     if not ckpt:
         raise SystemExit(f"{config}: no checkpoint: pass --ckpt or set model.checkpoint_filepath")
@@ -61,8 +59,7 @@ def main():
     ap.add_argument("--chunk", type=int, help="rays per render call (default: whole image for arch ngp, 16 384 for arch mlp)")
     args = ap.parse_args()
 
-    import train as cli
-    from robust_e_nerf_amd import data, engine, evaluation, ops
+    from robust_e_nerf_amd import checkpoint, config, data, evaluation, ops
     cfg, ckpt = load_config(args.config, args.ckpt)
     dev = "cuda:0"
     torch.cuda.set_device(0)
@@ -78,36 +75,11 @@ def main():
         Kinv = calib["Kinv"]
         raw = np.load(os.path.join(root, data.CAMERA_CALIBRATION))
         height, width = args.height or int(raw["img_height"]), args.width or int(raw["img_width"])
-    aabb = ncfg["aabb"]
-    if aabb == "auto":
-        aabb = torch.cat([tab_pos.min(0).values, tab_pos.max(0).values]).tolist()
-    ct = {"aabb": ops.AABB, "tanh": ops.UN_BOUNDED_TANH, "sphere": ops.UN_BOUNDED_SPHERE}[ncfg["contraction_type"]]
-    step_size = ncfg["render_step_size"]
-    if step_size == "auto":
-        step_size = max(aabb[3 + k] - aabb[k] for k in range(3)) * math.sqrt(3) / 1024
-    og = ncfg["occ_grid"]
-    rcfg = engine.RenderCfg(aabb=tuple(float(v) for v in aabb), contraction_type=ct, occ_res=(int(og["resolution"]),) * 3,
-                            near_plane=ncfg.get("near_plane"), far_plane=ncfg.get("far_plane"), render_step_size=float(step_size),
-                            cone_angle=float(ncfg["cone_angle"]), early_stop_eps=float(ncfg["early_stop_eps"]),
-                            alpha_thre=float(ncfg["alpha_thre"]), min_modeled_intensity=float(mcfg["min_modeled_intensity"]),
-                            mlp_precision=cfg.get("float32_matmul_precision", "highest"))
-    arch = ncfg.get("arch", "ngp")
-    for k_, v_ in cli.activation_fields(ncfg, arch).items():
-        setattr(rcfg, k_, v_)
+    rcfg = config.render_cfg(cfg, tab_pos)
     sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
-    C = int(sd[cli.PREFIX + ("mlp.rgb_layer.output_layer.bias" if arch == "mlp" else cli.NGP_KEYS["head.bo"])].numel())
-    if arch == "mlp":
-        from robust_e_nerf_amd import vanilla
-        fld = vanilla.VanillaField(dev, C, weight_norm=cli.weight_norm_flags(ncfg, arch))
-        cli.load_field_state_dict(fld, arch, sd)
-        r = vanilla.VanillaRenderer(fld, rcfg)
-    else:
-        fld = engine.NGPField(dev, C, ncfg.get("ngp", {}).get("pos_encoding"), weight_norm=cli.weight_norm_flags(ncfg, arch))
-        cli.load_field_state_dict(fld, arch, sd)
-        r = engine.Renderer(fld, rcfg)
-    r.binary.copy_(sd[cli.OCC + "_binary"].reshape(-1).to(torch.uint8).to(dev))
-    bk_key = "nerf.parametrizations.render_bkgd.original"
-    bkgd = torch.nn.functional.softplus(sd[bk_key].to(dev, torch.float32).reshape(-1)) if bk_key in sd else None
+    arch = ncfg.get("arch", "ngp")
+    fld, r = config.make_renderer(ncfg, rcfg, checkpoint.radiance_dim(sd, arch), dev)
+    bkgd = checkpoint.load_render_state(sd, fld, r, arch)
 
     os.makedirs(args.out, exist_ok=True)
     from PIL import Image

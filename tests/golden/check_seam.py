@@ -11,8 +11,8 @@ third-party package is stubbed as in make_golden.py) and checks, per reference t
    models/robust_e_nerf.py:207-259) CONSTRUCTS over the seam modules, for ``arch: ngp`` and ``arch: mlp``;
 2. every keyword the reference passes at its nerfacc / tinycudann call sites (parsed from the reference's sources
    with ``ast``) is accepted by the seam function of the same name;
-3. its state-dict keys and shapes equal the ones ``scripts/train.py`` writes into a checkpoint, and a checkpoint
-   state dict written by ``scripts/train.py``'s own code loads with ``strict=True`` into the reference module;
+3. its state-dict keys and shapes equal the ones ``checkpoint.model_state_dict`` writes into a checkpoint, and that
+   state dict loads with ``strict=True`` into the reference module;
 4. the seam ``OccupancyGrid`` carries nerfacc 0.3.1's persistent buffers (``_roi_aabb``, ``_binary``,
    ``resolution``, ``occs``).
 
@@ -30,7 +30,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(REPO, "scripts"))
 REF = "/root/reference"
 
 
@@ -80,8 +79,8 @@ def main():
     if not os.path.isdir(REF):
         raise SystemExit("build container only: /root/reference is absent")
     EasyDict, nerfacc_api, tcnn_api = install()
-    import train as cli                                # scripts/train.py
-    from robust_e_nerf_amd import engine, vanilla
+    from types import SimpleNamespace as NS
+    from robust_e_nerf_amd import checkpoint, engine, vanilla
     failures = []
 
     def check(ok, msg):
@@ -113,7 +112,7 @@ def main():
                 continue
             check(True, f"{tag}: reference NeRF constructs over nerfacc_api / tcnn_api")
             rsd = {"nerf." + k: v for k, v in ref.state_dict().items()}
-            # what scripts/train.py writes for the same configuration (its own code, on the CPU)
+            # what scripts/train.py writes for the same configuration (the writer's own code, on stand-ins on the CPU)
             res = cfg["model"]["nerf"]["occ_grid"]["resolution"]
             res = (res,) * 3 if isinstance(res, int) else tuple(res)
             if arch == "ngp":
@@ -121,12 +120,12 @@ def main():
                 fld.flat.normal_()
             else:
                 fld = vanilla.VanillaField("cpu", 1)
-            sd = cli.field_state_dict(fld, arch, aabb)
-            sd["nerf.parametrizations.render_bkgd.original"] = torch.ones(1)
-            sd[cli.OCC + "_roi_aabb"] = torch.tensor(aabb, dtype=torch.float32)
-            sd[cli.OCC + "_binary"] = torch.zeros(res, dtype=torch.bool)
-            sd[cli.OCC + "resolution"] = torch.tensor(res, dtype=torch.int32)
-            sd[cli.OCC + "occs"] = torch.zeros(res[0] * res[1] * res[2])
+            cells = res[0] * res[1] * res[2]
+            r = NS(field=fld, cfg=engine.RenderCfg(aabb=tuple(aabb), occ_res=res), occs=torch.zeros(cells),
+                   binary=torch.zeros(cells, dtype=torch.uint8))
+            tr = NS(r=r, t=engine.TrainCfg(bkgd_is_param=True), ct=torch.zeros(4), tau_raw=torch.zeros((), dtype=torch.float64),
+                    small=torch.ones(4))
+            sd = {k: v for k, v in checkpoint.model_state_dict(tr, arch).items() if k.startswith("nerf.")}
             only_ref, only_cli = sorted(set(rsd) - set(sd)), sorted(set(sd) - set(rsd))
             check(not only_ref and not only_cli, f"{tag}: state-dict keys equal ({len(rsd)} keys)" +
                   (f" -- only in the reference: {only_ref}; only in the CLI checkpoint: {only_cli}" if only_ref or only_cli else ""))

@@ -104,14 +104,12 @@ def test_batcher_shapes_ranges_and_rank_seeding():
 
 
 def test_cli_rejects_unsupported_hyperparameters():
-    """scripts/train.py:check_supported -- every shipped reference config shape passes; alternatives the kernels do not
+    """config.check_supported -- every shipped reference config shape passes; alternatives the kernels do not
     implement raise NotImplementedError instead of silently training something else."""
-    import copy, importlib.util, os
+    import copy, os
     import pytest
+    from robust_e_nerf_amd import config as cli
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("train_cli", os.path.join(repo, "scripts", "train.py"))
-    cli = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cli)
     import yaml
     ncfg = yaml.safe_load(open(os.path.join(repo, "configs", "synthetic_smoke.yaml")))["model"]["nerf"]
     ncfg["ngp"] = {"pos_encoding": {"otype": "HashGrid", "n_levels": 16, "n_features_per_level": 2, "interpolation": "Linear"},
@@ -228,9 +226,8 @@ def test_reference_train_yamls_are_accepted_by_the_cli_schema():
     kernels implement (check_supported).  The configs as parsed settings, one JSON string per file (fixture
     train_configs.npz written by tests/golden/make_golden.py::gen_train_configs); the GPU-side CLI tests use the repo's own
     files with the same settings."""
-    import json, os, sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-    import train as cli
+    import json
+    from robust_e_nerf_amd import config as cli
     g = np.load(os.path.join(GOLD, "train_configs.npz"))
     assert len(g.files) >= 4
     for f in g.files:

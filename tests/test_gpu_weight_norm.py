@@ -75,9 +75,7 @@ def test_weight_norm_training_steps_vs_oracle(amd, full_table_cache):
     autograd through its reparametrisation helper, then three optimiser steps -- (g, v) move exactly as torch.optim.Adam
     moves them, the effective block follows, the loss goes down; checkpoint keys weight_g / weight_v round-trip."""
     from oracle import field as ofield, hashgrid, step as ostep
-    import sys, os
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-    import train as cli
+    from robust_e_nerf_amd import checkpoint as cli
     ops, engine = amd
     spec = hashgrid.make_spec()
     g = load_golden("training_step_grad")

@@ -18,7 +18,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import bench
-from robust_e_nerf_amd import engine, evaluation, ops
+from robust_e_nerf_amd import checkpoint, config, engine, evaluation, ops
 
 DEV = "cuda:0"
 AABB = (-1.5, -1.5, -1.5, 1.5, 1.5, 1.5)
@@ -134,22 +134,11 @@ def novel_views(n=6):
 
 
 def evaluate(ckpt, Kinv_d, cfg, png=None):
-    sys.path.insert(0, os.path.join(REPO, "scripts"))
-    import train as cli
     sd = torch.load(ckpt, map_location="cpu")["state_dict"]
-    arch = cfg["model"]["nerf"].get("arch", "ngp")
+    ncfg = cfg["model"]["nerf"]
     rcfg = engine.RenderCfg(aabb=AABB, sampler="occgrid", render_step_size=3 * math.sqrt(3) / 1024)
-    if arch == "mlp":
-        from robust_e_nerf_amd import vanilla
-        fld = vanilla.VanillaField(DEV, 1)
-        cli.load_field_state_dict(fld, "mlp", sd)
-        r = vanilla.VanillaRenderer(fld, rcfg)
-    else:
-        fld = engine.NGPField(DEV, 1)
-        cli.load_field_state_dict(fld, "ngp", sd)
-        r = engine.Renderer(fld, rcfg)
-    r.binary.copy_(sd[cli.OCC + "_binary"].reshape(-1).to(torch.uint8).to(DEV))
-    bk = torch.nn.functional.softplus(sd["nerf.parametrizations.render_bkgd.original"].to(DEV))
+    fld, r = config.make_renderer(ncfg, rcfg, 1, DEV)
+    bk = checkpoint.load_render_state(sd, fld, r, ncfg.get("arch", "ngp"))
     gts, preds = [], []
     for pos, rot in novel_views():
         gts.append(render_scene(Kinv_d, pos, rot) + 1e-3)

@@ -204,6 +204,17 @@ int ren_hashgrid_bwd(const ren_grid_desc *grid, float *grad_table, const float *
                      const ren_scene_desc *scene, const float *rays_o, const float *rays_d,
                      const int32_t *ray_indices, const float *t_starts, const float *t_ends,
                      int64_t n, int32_t layout, const float *dfeat, void *stream);
+/* Reverse-mode gradient w.r.t. the POSITION (tcnn's grid backward-input; csrc/ren_normals.hip):
+ *   dx[i, :] = sum_l sum_f dfeat[i, l, f] * d feat[i, l, f] / d x[i, :]        dx[n, 3] float32, every row written
+ * Positions and dfeat layouts as ren_hashgrid_fwd.  With x_unit the gradient is w.r.t. the unit-cube position (scene is
+ * not read); from the sample stream it is the WORLD-space gradient at the sample midpoint: the unit-cube gradient times
+ * the transposed Jacobian of the contraction (aabb, sphere, tanh).  The interpolation weights are piecewise linear, so the
+ * gradient is the one of the cell ren_hashgrid_fwd reads for that point (it jumps at cell faces).  One launch, 128 corner
+ * reads per sample, no atomics, reads the table only; deterministic. */
+int ren_hashgrid_bwd_input(const ren_grid_desc *grid, const float *table, const float *x_unit,
+                           const ren_scene_desc *scene, const float *rays_o, const float *rays_d,
+                           const int32_t *ray_indices, const float *t_starts, const float *t_ends,
+                           int64_t n, int32_t layout, const float *dfeat, float *dx, void *stream);
 
 /* Same result as ren_hashgrid_bwd (grad_table += scatter of dfeat) but WITHOUT per-update global
  * atomics: the updates are counting-sorted by 16 384-entry table bin into `workspace` (HBM) and

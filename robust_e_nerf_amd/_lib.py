@@ -55,6 +55,7 @@ SIGNATURES = {
     "ren_pack_info": (c_int, [P, c_int64, c_int64, P, P, P]),
     "ren_hashgrid_fwd": (c_int, [POINTER(GridDesc), P, P, POINTER(SceneDesc), P, P, P, P, P, c_int64, c_int32, P, P, P]),
     "ren_hashgrid_bwd": (c_int, [POINTER(GridDesc), P, P, POINTER(SceneDesc), P, P, P, P, P, c_int64, c_int32, P, P]),
+    "ren_hashgrid_bwd_input": (c_int, [POINTER(GridDesc), P, P, POINTER(SceneDesc), P, P, P, P, P, c_int64, c_int32, P, P, P]),
     "ren_hashgrid_bwd_binned_workspace_bytes": (c_int64, [c_int64]),
     "ren_hashgrid_bwd_binned": (c_int, [POINTER(GridDesc), P, P, POINTER(SceneDesc), P, P, P, P, P, c_int64, c_int32, P, P, P, P]),
     "ren_hashgrid_bwd_binned_begin": (c_int, [POINTER(GridDesc), P, POINTER(SceneDesc), P, P, P, P, P, c_int64, c_int32, P, P]),

@@ -320,6 +320,7 @@ class Renderer:
         self._ws = torch.empty(max(ops.mlp_bwd_workspace_floats(fld.C), ops.mlp_bwd_x_workspace_floats(fld.C)),
                                device=dev, dtype=torch.float32)
         self._bin_ws, self._bin_ws_small = None, 0
+        self._normal_scratch = None                 # density_gradient: where the MLP backward's unused parameter gradient goes
         self._occ_scratch = None
         self._occ_gen = None
         self.grad_sync = None                       # parallel.GradSync of the Trainer under data parallelism
@@ -783,6 +784,45 @@ class Renderer:
         _, sigma, _ = ops.mlp_fwd(self._mlp_params(), f.C, feat, self.scene, x_world=x_world, n=n, density_only=True,
                                   bf16=self.cfg.mlp_bf16, act=self._act_code)
         return sigma
+
+    # ---- density gradient (surface normals): evaluation only, touches no training state ----------------------
+    def _density_gradient_stream(self, o, d, samples, n):
+        """(sigma (n,), d sigma / d x_world (n, 3)) at the midpoints of a packed sample stream: encoder, the exact-f32
+        density MLP, its backward seeded with d sigma = 1 / d rgb = 0 (d sigma / d feat), and the encoder's input gradient
+        (ops.hashgrid_bwd_input) through the contraction.  The MLP backward's parameter gradient goes to a scratch block;
+        the field's gradient buffers are not written.  A sample outside the box (selector 0) has sigma = 0 identically, so
+        its d sigma / d feat -- and with it the gradient -- is exactly zero.
+        The features and sigma come through ren_hashgrid_fwd's ren_contract, the gradient through contract_jvp's expression of
+        the same unit position (two spellings of one formula; the tests hold their agreement to round-off).  `_ws` is the
+        workspace the training backward uses too: both run on the current stream, so they take turns."""
+        f = self.field
+        dev = f.flat.device
+        if self._normal_scratch is None:                 # takes the MLP backward's parameter gradient: written, never read
+            self._normal_scratch = torch.empty(f.n_mlp, device=dev, dtype=torch.float32)
+        self._normal_scratch.zero_()
+        feat = ops.hashgrid_fwd(f.grid, f.table, scene=self.scene, rays=(o, d), samples=samples, n=n, layout=1)
+        mp = f.mlp                                       # effective (weight-normalised) parameters, fp32 whatever the training mode
+        _, sigma, base = ops.mlp_fwd(mp, f.C, feat, self.scene, rays=(o, d), samples=samples, n=n, density_only=True,
+                                     save_base=True, act=self._act_code)
+        zero_rgb = torch.zeros(n, f.C, device=dev, dtype=torch.float32)
+        dfeat = ops.mlp_bwd(mp, f.C, feat, base, self.scene, rays=(o, d), samples=samples, n=n, rgb=zero_rgb, d_rgb=zero_rgb,
+                            d_sigma=torch.ones(n, device=dev, dtype=torch.float32),
+                            grad_mlp_params=self._normal_scratch, workspace=self._ws,
+                            act=self._act_code)
+        grad = ops.hashgrid_bwd_input(f.grid, f.table, dfeat, scene=self.scene, rays=(o, d), samples=samples, n=n, layout=1)
+        return sigma, grad
+
+    def density_gradient(self, x_world: torch.Tensor):
+        """-> sigma (n,), grad (n, 3) = d sigma / d x_world in world space, for arbitrary world points (each taken as a
+        zero-length ray, so the kernels see exactly the point).  Zero gradient outside the box."""
+        x = x_world.detach().to(torch.float32).contiguous()
+        n = x.shape[0]
+        dev = x.device
+        if n == 0:
+            return torch.zeros(0, device=dev), torch.zeros(0, 3, device=dev)
+        zero = torch.zeros(n, device=dev, dtype=torch.float32)
+        samples = (torch.arange(n, device=dev, dtype=torch.int32), zero, zero)
+        return self._density_gradient_stream(x, torch.zeros_like(x), samples, n)
 
     # ---- occupancy grid (K14): nerfacc OccupancyGrid.every_n_step as driven by nerf.py:170-204 ------------
     def update_occ_grid(self, step: int, cam_positions: Optional[torch.Tensor] = None,

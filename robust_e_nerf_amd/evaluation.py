@@ -72,6 +72,66 @@ def render_image(r: Renderer, Kinv: torch.Tensor, cam_pos: torch.Tensor, cam_rot
     return img, out_o.view(height, width), out_d.view(height, width)
 
 
+# ---- surface normals: the composited direction of -grad(sigma) (arch ngp) ------------------------------------------------
+@torch.no_grad()
+def render_normals(r: Renderer, Kinv: torch.Tensor, px: torch.Tensor, pos: torch.Tensor, rot: torch.Tensor):
+    """Normal map for (N, 2) pixels with per-pixel poses, over the rays and samples render_pixels takes (no jitter, the
+    occupancy grid, the visibility pass): per sample n_i = -grad sigma_i / max(|grad sigma_i|, 1e-12), per ray
+    N = sum_i w_i n_i with the render weights (the compositing kernel, the normals as a 3-channel colour, no background).
+    -> world-space normals (N, 3), opacity (N,), camera-frame normals R^T N (N, 3) (camera axes = the columns of `rot`, the
+    convention render_pixels turns ray distance into z-depth with).  |N| <= opacity; rays without samples give zeros."""
+    if not isinstance(r.field, NGPField):
+        raise NotImplementedError("normals: arch ngp only")
+    rot = rot.contiguous()
+    o, d = ops.raygen(Kinv, px.contiguous(), pos.contiguous(), rot)
+    pk = r.sample(o, d, None, False)
+    n_rays = o.shape[0]
+    if pk.n == 0:
+        zero = torch.zeros(n_rays, 3, device=o.device)
+        return zero, torch.zeros(n_rays, device=o.device), zero.clone()
+    sigma, grad = r._density_gradient_stream(o, d, (pk.ray_indices, pk.t_starts, pk.t_ends), pk.n)
+    nrm = (-grad / grad.norm(dim=-1, keepdim=True).clamp_min(1e-12)).contiguous()
+    world, opac, _, _, _ = ops.composite_fwd(pk.offsets, pk.counts, pk.t_starts, pk.t_ends, sigma, nrm, 3, None, save=False)
+    cam = (rot * world[:, :, None]).sum(1)                             # R^T N
+    return world, opac, cam
+
+
+@torch.no_grad()
+def render_normal_image(r: Renderer, Kinv: torch.Tensor, cam_pos: torch.Tensor, cam_rot: torch.Tensor, height: int,
+                        width: int, chunk: Optional[int] = None, rows: Optional[Tuple[int, int]] = None):
+    """(3, H, W) camera-frame normal map and (H, W) opacity for one pose, chunked as render_image (whose `chunk` / `rows`
+    these are); the result does not depend on the chunking."""
+    if not isinstance(r.field, NGPField):
+        raise NotImplementedError("normals: arch ngp only")
+    if chunk is None:
+        chunk = 1 << 20
+    dev = Kinv.device
+    px = pixel_grid(height, width, dev)
+    if rows is not None:
+        px = px[rows[0]: rows[1]]
+        height = rows[1] - rows[0]
+    px = px.reshape(-1, 2)
+    n = px.shape[0]
+    out_n = torch.empty(n, 3, device=dev)
+    out_o = torch.empty(n, device=dev)
+    for s in range(0, n, chunk):
+        e = min(s + chunk, n)
+        pos = cam_pos.reshape(1, 3).expand(e - s, 3).contiguous()
+        rot = cam_rot.reshape(1, 3, 3).expand(e - s, 3, 3).contiguous()
+        _, out_o[s:e], out_n[s:e] = render_normals(r, Kinv, px[s:e], pos, rot)
+    return out_n.view(height, width, 3).permute(2, 0, 1).contiguous(), out_o.view(height, width)
+
+
+def normal_png(normals: torch.Tensor, opacity: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
+    """The usual colour code of a (3, H, W) normal map: round(255 (n / max(|n|, eps) + 1) / 2) per component, pixels of
+    opacity 0 white -> uint8 (H, W, 3) on the CPU"""
+    n = normals.detach().cpu().to(torch.float32)
+    unit = n / n.norm(dim=0, keepdim=True).clamp_min(eps)
+    u8 = (255 * (unit + 1) / 2).round().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+    u8[opacity.detach().cpu() == 0] = 255
+    return u8
+
+
 # ---- data-parallel evaluation: collective C3 of SURVEY 2.3 (`self.all_gather(outputs)`, robust_e_nerf.py:591) ------------
 def view_shard(n_views: int, rank: int, world: int):
     """indices of the evaluation views this rank renders: torch's DistributedSampler(shuffle=False) as Lightning's DDP

@@ -388,6 +388,24 @@ def hashgrid_bwd(grid: GridDesc, grad_table, dfeat, *, x_unit=None, scene=None, 
                                        _ptr(dfeat, torch.float32), _stream()), "ren_hashgrid_bwd")
 
 
+def hashgrid_bwd_input(grid: GridDesc, table, dfeat, *, x_unit=None, scene=None, rays=None, samples=None,
+                       n: int, layout: int, out=None):
+    """dx (n, 3) = J_x^T dfeat of the encoding, one launch (csrc/ren_normals.hip).  x_unit: gradient w.r.t. the unit-cube
+    position; scene + rays + samples: world-space gradient at the sample midpoints (through the contraction)."""
+    if out is None:
+        out = torch.empty(n, 3, device=table.device, dtype=torch.float32)
+    if n == 0:                                           # empty tensors have no storage: their null pointers are no bad arguments
+        return out
+    o, d = rays if rays is not None else (None, None)
+    ri, ts, te = samples if samples is not None else (None, None, None)
+    check(_lib.load().ren_hashgrid_bwd_input(ctypes.byref(grid), _ptr(table, torch.float32), _ptr(x_unit),
+                                             ctypes.byref(scene) if scene is not None else None,
+                                             _ptr(o), _ptr(d), _ptr(ri), _ptr(ts), _ptr(te), n, layout,
+                                             _ptr(dfeat, torch.float32), _ptr(out, torch.float32), _stream()),
+          "ren_hashgrid_bwd_input")
+    return out
+
+
 def hashgrid_bwd_binned_workspace_bytes(n: int) -> int:
     return int(_lib.load().ren_hashgrid_bwd_binned_workspace_bytes(n))
 
@@ -843,7 +861,7 @@ def occgrid_binarize(occs, occ_thre: float, binary, scratch):
 # disabled (zero overhead) otherwise.
 _PROFILE = None
 _TIMED = ("ray_aabb_intersect", "ray_march_count", "ray_march_write", "exclusive_scan", "visibility",
-          "compact_samples", "compact_features", "hashgrid_fwd", "hashgrid_bwd", "hashgrid_bwd_binned", "hashgrid_bwd_binned_begin",
+          "compact_samples", "compact_features", "hashgrid_fwd", "hashgrid_bwd", "hashgrid_bwd_input", "hashgrid_bwd_binned", "hashgrid_bwd_binned_begin",
           "hashgrid_bwd_binned_scatter", "hashgrid_bwd_binned_finish", "mlp_fwd", "mlp_bwd", "mlp_fwd_save",
           "mlp_bwd_saved", "mlp_fwd_x", "mlp_bwd_x", "composite_fwd",
           "composite_bwd", "column_sum", "event_loss_fwd", "event_loss_bwd", "adam_step", "trajectory", "raygen")

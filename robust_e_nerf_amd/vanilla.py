@@ -673,6 +673,12 @@ class VanillaRenderer(Renderer):
             del B
         return out
 
+    def _density_gradient_stream(self, o, d, samples, n):
+        raise NotImplementedError("normals: arch ngp only")
+
+    def density_gradient(self, x_world: torch.Tensor):
+        raise NotImplementedError("normals: arch ngp only")
+
     def query(self, x_world: torch.Tensor, dirs: torch.Tensor):
         """field(x, d) -> (rgb (n, C), sigma (n,), buffers) for free-standing points (mlp.py:349-358)."""
         n = x_world.shape[0]

@@ -3,7 +3,7 @@
 reference (same state-dict keys).
 
     python scripts/render.py --config <YAML> --ckpt runs/train/last.ckpt --out renders/ \
-        [--dataset-dir DIR | --synthetic] [--every 50] [--height 260 --width 346] [--gt-dir DIR]
+        [--dataset-dir DIR | --synthetic] [--every 50] [--height 260 --width 346] [--gt-dir DIR] [--normals]
     python scripts/render.py --config <test YAML> --stage test --out renders/      # --ckpt: model.checkpoint_filepath
 
 Poses come from the dataset's camera_poses.npz (every `--every`-th pose) or from the synthetic benchmark orbit; the
@@ -13,7 +13,9 @@ linear intensity images of the same size) the prediction is aligned to the groun
 log space and the PSNR of every view and their mean are printed (metric.py:60-72).  With --stage val | test the
 dataset's posed views are scored as the reference's validation / test epochs score them: aligned L1, PSNR and SSIM per
 view and their means (metric.py:54-81), and with model.eval_save_pred_intensity_img the aligned predictions are written
-to <out>/predictions/<sample_id>.png (robust_e_nerf.py:736-780).
+to <out>/predictions/<sample_id>.png (robust_e_nerf.py:736-780).  With --normals (arch ngp) every view's surface-normal map --
+the composited direction of -grad(sigma), camera frame -- is written as <out>/normals/<index>.png (RGB = (n + 1) / 2,
+transparent pixels white) and added to views.npz as `normal` (float32, (views, 3, H, W)).
 """
 import argparse
 import os
@@ -57,6 +59,8 @@ def main():
                          "layout) instead of rendering along the trajectory: aligned L1 / PSNR / SSIM per view and their means, as "
                          "the reference's validation / test epochs (robust_e_nerf.py:519-696)")
     ap.add_argument("--chunk", type=int, help="rays per render call (default: whole image for arch ngp, 16 384 for arch mlp)")
+    ap.add_argument("--normals", action="store_true",
+                    help="also write surface-normal maps (camera frame) to <out>/normals/<index>.png and views.npz (arch ngp)")
     args = ap.parse_args()
 
     from robust_e_nerf_amd import checkpoint, config, data, evaluation, ops
@@ -78,6 +82,10 @@ def main():
     rcfg = config.render_cfg(cfg, tab_pos)
     sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
     arch = ncfg.get("arch", "ngp")
+    if args.normals and arch != "ngp":
+        raise SystemExit("--normals: arch ngp only")
+    if args.normals and args.stage:
+        raise SystemExit("--normals renders along the trajectory; it has no meaning with --stage")
     fld, r = config.make_renderer(ncfg, rcfg, checkpoint.radiance_dim(sd, arch), dev)
     bkgd = checkpoint.load_render_state(sd, fld, r, arch)
 
@@ -99,7 +107,9 @@ def main():
     Kinv_d = Kinv.to(dev, torch.float32)
     idx = list(range(0, tab_ts.shape[0], max(1, args.every)))
     pos_all, rot_all = ops.trajectory(tab_ts[idx].to(dev, torch.float64), tab_ts.to(dev), tab_pos.to(dev), tab_quat.to(dev))
-    imgs, opacs, depths, scores = [], [], [], []
+    imgs, opacs, depths, scores, normals = [], [], [], [], []
+    if args.normals:
+        os.makedirs(os.path.join(args.out, "normals"), exist_ok=True)
     for k, i in enumerate(idx):
         img, opac, depth = evaluation.render_image(r, Kinv_d, pos_all[k], rot_all[k], height, width, bkgd=bkgd, chunk=args.chunk)
         imgs.append(img.cpu()); opacs.append(opac.cpu()); depths.append(depth.cpu())
@@ -113,8 +123,14 @@ def main():
         if u8.ndim == 3:
             u8 = np.transpose(u8, (1, 2, 0))
         Image.fromarray(u8, mode="L" if u8.ndim == 2 else "RGB").save(os.path.join(args.out, f"{i}.png"))
+        if args.normals:
+            nrm, n_opac = evaluation.render_normal_image(r, Kinv_d, pos_all[k], rot_all[k], height, width, chunk=args.chunk)
+            normals.append(nrm.cpu())
+            Image.fromarray(evaluation.normal_png(nrm, n_opac).numpy(), mode="RGB").save(
+                os.path.join(args.out, "normals", f"{i}.png"))
+    extra = dict(normal=torch.stack(normals).numpy()) if args.normals else {}
     np.savez(os.path.join(args.out, "views.npz"), index=np.array(idx), intensity=torch.stack(imgs).numpy(),
-             opacity=torch.stack(opacs).numpy(), depth=torch.stack(depths).numpy())
+             opacity=torch.stack(opacs).numpy(), depth=torch.stack(depths).numpy(), **extra)
     msg = f"{len(idx)} views of {height} x {width} written to {args.out}"
     if scores:
         msg += f"; mean PSNR {sum(scores) / len(scores):.2f} dB"

@@ -785,6 +785,34 @@ int64_t ren_ssim_scratch_doubles(int64_t P, int32_t H, int32_t W);
 int ren_ssim_planes(const float *pred, const float *target, int64_t P, int32_t H, int32_t W, double data_range,
                     double *out, double *scratch, void *stream);
 
+/* ---- event frames (csrc/ren_event_frames.hip) -------------------------------------------------------- *
+ * Recorded events against the model's predicted brightness change: between the times edges[v] and edges[v + 1] pixel u saw
+ * n+ positive and n- negative events, and the sensor model says log I(u, t1) - log I(u, t0) ~ c_p n+ - c_n n- to within one
+ * threshold.  ren_event_frames bins the raw stream as raw_events.npz stores it -- position: N words x | y << 16 (an (N, 2)
+ * uint16 array read as one 32-bit word per event), timestamp: N int64 nanoseconds in time order, polarity: N bytes, non-zero
+ * = positive -- into counts, int32 (V, 2, H, W), plane 0 the positives and plane 1 the negatives.  The CALLER zeroes counts;
+ * the call adds to it.  Event e belongs to window v iff edges[v] <= timestamp[e] < edges[v + 1] (edges: V + 1 int64 on the
+ * device, non-decreasing -- not checked here; among equal edges the window before them is empty); events before edges[0], at
+ * or after edges[V], or with x >= W or y >= H are dropped.  The window is found by a binary search per event, over a copy of
+ * the edges in LDS while V + 1 <= REN_EVENT_FRAMES_LDS_EDGES and over global memory above that.  Integer atomics: the sums
+ * are exact and independent of arrival order, repeated calls are bitwise equal.  flags: 0, or REN_EVENT_FRAMES_MERGE -- the
+ * lanes of a wave that add to one counter are merged into one atomic (same result).
+ * REN_ERR_BAD_ARG for a null edges / counts, a null event array with N > 0, N < 0, V < 1, H * W == 0 or an unknown flag,
+ * before any launch; N == 0 launches nothing. */
+#define REN_EVENT_FRAMES_LDS_EDGES 4096
+#define REN_EVENT_FRAMES_MERGE 1
+int ren_event_frames(const uint32_t *position, const int64_t *timestamp, const uint8_t *polarity, int64_t N,
+                     const int64_t *edges, int32_t V, int32_t H, int32_t W, int32_t flags, int32_t *counts, void *stream);
+/* Per-window comparison of the measured change m = c_p n+ - c_n n- (formed in fp64 from counts) with pred, float32 (V, H, W),
+ * over the pixels with valid (uint8 (V, H, W)) != 0: out, float64 (V, 9) =
+ *   [count, sum m, sum p, sum m^2, sum p^2, sum m p, sum (p - m)^2, #{|p - m| <= max(c_p, c_n)}, #{n+ + n- > 0}].
+ * Two launches (tile partials, then a fixed-order sum per window), no float atomics: bitwise repeatable.
+ * scratch: ren_event_frame_compare_scratch_doubles(V, H, W) doubles of device memory (0 for V < 1 or H * W == 0).
+ * REN_ERR_BAD_ARG for a null pointer, V < 1, H * W == 0 or a c_p / c_n that is not finite. */
+int64_t ren_event_frame_compare_scratch_doubles(int32_t V, int32_t H, int32_t W);
+int ren_event_frame_compare(const int32_t *counts, const float *pred, const uint8_t *valid, int32_t V, int32_t H, int32_t W,
+                            double c_p, double c_n, double *out, double *scratch, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

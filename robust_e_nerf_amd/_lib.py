@@ -155,6 +155,9 @@ SIGNATURES = {
     "ren_grad_loss_bwd": (c_int, [P, P, P, P, c_int64, c_int32, c_float, P, P, P, P, P, P]),
     "ren_ssim_scratch_doubles": (c_int64, [c_int64, c_int32, c_int32]),
     "ren_ssim_planes": (c_int, [P, P, c_int64, c_int32, c_int32, c_double, P, P, P]),
+    "ren_event_frames": (c_int, [P, P, P, c_int64, P, c_int32, c_int32, c_int32, c_int32, P, P]),
+    "ren_event_frame_compare_scratch_doubles": (c_int64, [c_int32, c_int32, c_int32]),
+    "ren_event_frame_compare": (c_int, [P, P, P, c_int32, c_int32, c_int32, c_double, c_double, P, P, P]),
 }
 
 _lib = None

@@ -666,8 +666,67 @@ def ssim_planes(pred: torch.Tensor, target: torch.Tensor, data_range: float) -> 
     return out
 
 
+# ------------------------------------------------------------------------------- event frames
+EVENT_FRAMES_LDS_EDGES = 4096        # REN_EVENT_FRAMES_LDS_EDGES: the edges are searched in LDS while V + 1 <= this
+EVENT_FRAMES_MERGE = 1               # REN_EVENT_FRAMES_MERGE
+
+
+def event_frames(position: torch.Tensor, timestamp: torch.Tensor, polarity: torch.Tensor, edges: torch.Tensor, height: int,
+                 width: int, merge: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the raw stream of raw_events.npz on the device -- position (N, 2) uint16 (x, y) [or (N,) int32 words x | y << 16],
+    timestamp (N,) int64 in time order, polarity (N,) bool / uint8 -- binned into the windows [edges[v], edges[v + 1]) of
+    `edges` (V + 1,) int64: -> counts (V, 2, H, W) int32, plane 0 the positive and plane 1 the negative events.  Events
+    outside every window or outside the image are dropped.  Integer atomics: exact, bitwise repeatable.  `merge`: one atomic
+    per distinct counter of a wave (same result).  `out`: add to these counts instead of to zeros."""
+    n = timestamp.shape[0]
+    if position.dtype == torch.uint16 and position.dim() == 2 and position.shape == (n, 2):
+        words = position.contiguous().view(torch.int32).view(-1) if n else torch.empty(0, device=position.device, dtype=torch.int32)
+    elif position.dtype == torch.int32 and position.shape == (n,):
+        words = position.contiguous()
+    else:
+        raise ValueError(f"event_frames: position must be (N, 2) uint16 or (N,) int32 words; got {position.dtype} "
+                         f"{tuple(position.shape)} for {n} timestamps")
+    if polarity.shape != (n,) or polarity.dtype not in (torch.bool, torch.uint8, torch.int8):
+        raise ValueError(f"event_frames: polarity must be (N,) bool / uint8; got {polarity.dtype} {tuple(polarity.shape)}")
+    if edges.dim() != 1 or edges.shape[0] < 2:
+        raise ValueError("event_frames: edges must hold at least two times")
+    V = edges.shape[0] - 1
+    if out is None:
+        out = torch.zeros(V, 2, height, width, device=edges.device, dtype=torch.int32)
+    elif out.shape != (V, 2, height, width):
+        raise ValueError(f"event_frames: out must be ({V}, 2, {height}, {width}); got {tuple(out.shape)}")
+    check(_lib.load().ren_event_frames(_ptr(words), _ptr(timestamp.contiguous(), torch.int64), _ptr(polarity.contiguous()), n,
+                                       _ptr(edges.contiguous(), torch.int64), V, height, width,
+                                       EVENT_FRAMES_MERGE if merge else 0, _ptr(out, torch.int32), _stream()), "ren_event_frames")
+    return out
+
+
+def event_frame_compare_scratch_doubles(V: int, H: int, W: int) -> int:
+    return int(_lib.load().ren_event_frame_compare_scratch_doubles(V, H, W))
+
+
+def event_frame_compare(counts: torch.Tensor, pred: torch.Tensor, valid: torch.Tensor, c_p: float, c_n: float) -> torch.Tensor:
+    """counts (V, 2, H, W) int32, pred (V, H, W) float32, valid (V, H, W) bool / uint8 -> (V, 9) float64 per window, over
+    the pixels with valid != 0 and with m = c_p n+ - c_n n- in float64:
+    [count, sum m, sum p, sum m^2, sum p^2, sum m p, sum (p - m)^2, #{|p - m| <= max(c_p, c_n)}, #{n+ + n- > 0}].
+    Two launches, fixed-order sums, no float atomics: bitwise repeatable."""
+    if counts.dim() != 4 or counts.shape[1] != 2:
+        raise ValueError(f"event_frame_compare: counts must be (V, 2, H, W); got {tuple(counts.shape)}")
+    V, _, H, W = counts.shape
+    if pred.shape != (V, H, W) or valid.shape != (V, H, W):
+        raise ValueError(f"event_frame_compare: pred / valid must be ({V}, {H}, {W}); got {tuple(pred.shape)}, {tuple(valid.shape)}")
+    if valid.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"event_frame_compare: valid must be bool / uint8; got {valid.dtype}")
+    out = torch.empty(V, 9, device=counts.device, dtype=torch.float64)
+    scratch = torch.empty(max(1, event_frame_compare_scratch_doubles(V, H, W)), device=counts.device, dtype=torch.float64)
+    check(_lib.load().ren_event_frame_compare(_ptr(counts.contiguous(), torch.int32), _ptr(pred.contiguous(), torch.float32),
+                                              _ptr(valid.contiguous()), V, H, W, float(c_p), float(c_n), _ptr(out),
+                                              _ptr(scratch), _stream()), "ren_event_frame_compare")
+    return out
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
-ERR_FN = {"l1": 0, "mse": 1, "mape": 2}
+ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 
 
 PARAM_WEIGHT_POWER = {None: 0, "mean_contrast_reciprocal": 1, "mean_contrast_reciprocal_sq": 2}

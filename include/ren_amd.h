@@ -813,6 +813,35 @@ int64_t ren_event_frame_compare_scratch_doubles(int32_t V, int32_t H, int32_t W)
 int ren_event_frame_compare(const int32_t *counts, const float *pred, const uint8_t *valid, int32_t V, int32_t H, int32_t W,
                             double c_p, double c_n, double *out, double *scratch, void *stream);
 
+/* ---- event table (csrc/ren_event_table.hip) ---------------------------------------------------------- *
+ * raw_events.npz -> the training's event table (data/datasets.py:133-364: per-pixel intervals, Bayer channel, undistorted
+ * position) and tau_max (the minimum interval), device-resident, after ONE stable sort of the pixel keys by the caller.
+ * ren_event_intervals: pix_sorted: N int32 keys y * W + x in stable by-pixel order; order: N int64, the stream index of each
+ * sorted slot (a permutation of 0 .. N - 1); timestamp: N int64 in stream order.  For sorted slot i with j = order[i]:
+ * valid[j] = (i > 0 and pix_sorted[i] == pix_sorted[i - 1] and d != 0) with d = timestamp[j] - timestamp[order[i - 1]] -- the
+ * IMMEDIATE predecessor, kept or not -- and start_ts[j] = timestamp[order[i - 1]] where valid (other start_ts are not
+ * written).  *min_diff (one int64 on the device, set to INT64_MAX by the CALLER) becomes min(*min_diff, d over the valid
+ * slots): per wave, per workgroup, then one 64-bit atomic min per workgroup; bitwise repeatable.  An order entry outside
+ * [0, N) is skipped.
+ * ren_event_table_write: valid (N uint8) and offsets (N int32, the EXCLUSIVE prefix sum of valid) in stream order; position:
+ * (N, 2) (x, y) as the file stores it, position_bytes = 2 (uint16), 4 (int32) or 8 (int64) per coordinate; polarity: N bytes;
+ * M = sum of valid = rows of the outputs.  Kept event e writes row offsets[e]: out_position (M, 2) float32 = lut[y * W + x]
+ * (lut: (H * W, 2) float32, NULL = the coordinates cast to float32; a pixel outside W x H is cast as well, the CALLER checks
+ * the range), out_start_ts = start_ts[e], out_end_ts = timestamp[e], out_num_pos = polarity[e], out_num_neg = 1 -
+ * polarity[e] (int64 each), out_channel_idx (uint8) = bayer_channels[(x & 1) + 2 * (y & 1)] (bayer_channels: 4 bytes on the
+ * HOST in tile order TL, TR, BL, BR; NULL together with out_channel_idx for a monochrome sensor).  Rows keep stream order.
+ * Both: grid-stride loops, no workgroup waits on another.  REN_ERR_BAD_ARG for a null or misaligned required pointer, a
+ * negative size, M > N, H or W < 1, a position_bytes other than 2 / 4 / 8, or one of bayer_channels / out_channel_idx
+ * without the other, before any launch; REN_ERR_UNSUPPORTED for N or H * W >= 2^31; N == 0 or M == 0 launches nothing. */
+#define REN_EVENT_TABLE_THREADS 256          /* workgroup size of both kernels (at most 2 048 workgroups, grid-stride) */
+int ren_event_intervals(const int32_t *pix_sorted, const int64_t *order, const int64_t *timestamp, int64_t N, uint8_t *valid,
+                        int64_t *start_ts, int64_t *min_diff, void *stream);
+int ren_event_table_write(const uint8_t *valid, const int32_t *offsets, const void *position, int32_t position_bytes,
+                          const int64_t *timestamp, const int64_t *start_ts, const uint8_t *polarity, int64_t N, int64_t M,
+                          const float *lut, int32_t H, int32_t W, const uint8_t *bayer_channels, float *out_position,
+                          int64_t *out_start_ts, int64_t *out_end_ts, int64_t *out_num_pos, int64_t *out_num_neg,
+                          uint8_t *out_channel_idx, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

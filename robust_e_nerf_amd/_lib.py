@@ -158,6 +158,8 @@ SIGNATURES = {
     "ren_event_frames": (c_int, [P, P, P, c_int64, P, c_int32, c_int32, c_int32, c_int32, P, P]),
     "ren_event_frame_compare_scratch_doubles": (c_int64, [c_int32, c_int32, c_int32]),
     "ren_event_frame_compare": (c_int, [P, P, P, c_int32, c_int32, c_int32, c_double, c_double, P, P, P]),
+    "ren_event_intervals": (c_int, [P, P, P, c_int64, P, P, P, P]),
+    "ren_event_table_write": (c_int, [P, P, P, c_int32, P, P, P, c_int64, c_int64, P, c_int32, c_int32, P, P, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -18,7 +18,7 @@ STAMP = OUT + ".stamp"
 SOURCES = ["ren_api.hip", "ren_pose.hip", "ren_sampling.hip", "ren_composite.hip", "ren_train.hip",
            "ren_hashgrid.hip", "ren_hashgrid_binned.hip", "ren_mlp.hip", "ren_jvp.hip", "ren_mlp_jvp.hip",
            "ren_jvp2.hip", "ren_dense.hip", "ren_vfield.hip", "ren_mlp_x.hip", "ren_mlp_jvp_x.hip",
-           "ren_metrics.hip", "ren_normals.hip", "ren_event_frames.hip"]
+           "ren_metrics.hip", "ren_normals.hip", "ren_event_frames.hip", "ren_event_table.hip"]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           "-Wno-unused-result"]
 # the sampler must match the sequential oracle bit for bit: no FMA contraction there
@@ -40,7 +40,9 @@ PER_FILE = {"ren_sampling.hip": ["-ffp-contract=off"] + NO_SLP, "ren_jvp2.hip": 
             "ren_hashgrid.hip": NO_SLP, "ren_hashgrid_binned.hip": NO_SLP, "ren_normals.hip": NO_SLP,
             "ren_mlp_x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "ren_mlp_jvp_x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
             # the comparison sums are held to a float64 restatement term by term: no FMA contraction
-            "ren_event_frames.hip": ["-ffp-contract=off"] + NO_SLP}
+            "ren_event_frames.hip": ["-ffp-contract=off"] + NO_SLP,
+            # integer arithmetic and a table gather: nothing to pack
+            "ren_event_table.hip": NO_SLP}
 
 
 def _headers():

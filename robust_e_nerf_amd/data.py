@@ -187,6 +187,113 @@ def load_max_refractory_period(root: str) -> torch.Tensor:
     return max_refractory_period(raw["position"], raw["timestamp"], int(calib["img_width"]))
 
 
+# ------------------------------------------------------------------------------------------- raw -> table, on the device
+def undistortion_lut(calib) -> Optional[np.ndarray]:
+    """(H * W, 2) float32, row-major by pixel: `undistort_points` of the integer pixel grid, or None for a sensor without
+    distortion (the condition of `undistort_events`).  Event positions are integer pixels, so gathering this table at
+    y * W + x gives what `undistort_events` computes per event, bit for bit, after H * W points instead of N."""
+    dist = np.asarray(calib["distortion_params"]).reshape(-1)
+    if len(dist) == 0 or not np.any(dist != 0):
+        return None
+    W, H = int(calib["img_width"]), int(calib["img_height"])
+    y, x = np.divmod(np.arange(H * W, dtype=np.int64), W)
+    grid = np.stack([x, y], -1).astype(np.float64)
+    K = np.asarray(calib["intrinsics"], np.float64)
+    return undistort_points(grid, K, dist, str(calib["distortion_model"])).astype(np.float32)
+
+
+def _bayer_channels(bayer_pattern: str):
+    if bayer_pattern == "":
+        return None
+    assert len(bayer_pattern) == 4 and set(bayer_pattern) == set(COLOR_CHANNEL)
+    return [COLOR_CHANNEL[c] for c in bayer_pattern]
+
+
+def build_event_table(position, timestamp, polarity, calib, device):
+    """The raw stream of `raw_events.npz` -> (table, tau_max) with the table on `device`: what
+    `undistort_events(colorize_events(queue_raw_events(...)))` and `max_refractory_period` give, value for value, from one
+    stable sort by pixel and two launches (ops.event_intervals, ops.event_table_write).  The columns are uploaded
+    at their stored width; nothing but the number of kept events and the minimum interval comes back to the host.
+    Lengths and 0 <= x < img_width, 0 <= y < img_height are checked HERE, on the host arrays, before anything is uploaded:
+    that is what keeps the lookup-table gather in bounds.  tau_max: 0-dim float64, inf when no event is kept."""
+    from . import ops
+    position, timestamp, polarity = np.asarray(position), np.asarray(timestamp), np.asarray(polarity)
+    n = len(timestamp)
+    if position.ndim != 2 or position.shape[1] != 2 or len(position) != n or timestamp.shape != (n,) or polarity.shape != (n,):
+        raise ValueError(f"position (N, 2), timestamp (N,) and polarity (N,) must hold the same number of events; got "
+                         f"{position.shape}, {timestamp.shape}, {polarity.shape}")
+    if position.dtype.kind not in "iu" or timestamp.dtype.kind not in "iu" or polarity.dtype.kind not in "biu":
+        raise ValueError(f"integer position / timestamp and bool or integer polarity expected; got {position.dtype}, "
+                         f"{timestamp.dtype}, {polarity.dtype}")
+    W, H = int(calib["img_width"]), int(calib["img_height"])
+    if W < 1 or H < 1 or H * W > ops.EVENT_TABLE_MAX_N or n > ops.EVENT_TABLE_MAX_N:
+        raise NotImplementedError(f"{n} events on {W} x {H} pixels: both counts must stay below 2^31")
+    if n:
+        lo, hi = position.min(0), position.max(0)
+        if int(lo[0]) < 0 or int(lo[1]) < 0 or int(hi[0]) >= W or int(hi[1]) >= H:
+            raise ValueError(f"event positions span x {int(lo[0])} .. {int(hi[0])}, y {int(lo[1])} .. {int(hi[1])}: outside the "
+                             f"{W} x {H} sensor of the calibration")
+    if polarity.dtype not in (np.bool_, np.uint8):
+        if n and (int(polarity.min()) < 0 or int(polarity.max()) > 255):
+            raise ValueError("polarity must fit one byte")
+        polarity = polarity.astype(np.uint8)
+    if position.dtype not in (np.uint16, np.int32, np.int64):                    # in range: fits int32
+        position = position.astype(np.int32)
+    lut = undistortion_lut(calib)
+    names = calib.files if hasattr(calib, "files") else calib                    # an opened .npz or a dict
+    channels = _bayer_channels(str(calib["bayer_pattern"]) if "bayer_pattern" in names else "")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    pos, ts, pol = up(position), up(timestamp.astype(np.int64, copy=False)), up(polarity)
+    lut_d = None if lut is None else up(lut)
+    if n == 0:
+        empty = torch.empty(0, device=device, dtype=torch.int32)
+        table = ops.event_table_write(empty.to(torch.uint8), empty, pos, ts, ts, pol, 0, H, W, lut_d, channels)
+        return table, torch.tensor(float("inf"), dtype=torch.float64)
+    if pos.dtype == torch.uint16:                                                 # one word x | y << 16 per event
+        word = pos.view(torch.int32).view(-1)
+        pix = ((word >> 16) & 0xffff) * W + (word & 0xffff)
+    else:
+        pix = (pos[:, 1] * W + pos[:, 0]).to(torch.int32)
+    pix_sorted, order = torch.sort(pix, stable=True)
+    del pix
+    valid, start_ts, min_diff = ops.event_intervals(pix_sorted, order, ts)
+    del pix_sorted, order
+    offsets = torch.cumsum(valid, 0, dtype=torch.int32)
+    m, tau = (int(v) for v in torch.stack([offsets[-1].to(torch.int64), min_diff[0]]).cpu())      # the one host read
+    offsets.sub_(valid)                                                           # inclusive -> exclusive
+    table = ops.event_table_write(valid, offsets, pos, ts, start_ts, pol, m, H, W, lut_d, channels)
+    return table, torch.tensor(float(tau) if m else float("inf"), dtype=torch.float64)
+
+
+def load_event_table(root: str, permutation_seed: Optional[int] = None, use_cache: bool = True, device="cuda"):
+    """`load_events` + `load_max_refractory_period` in one pass -> (event table on `device`, tau_max).  With `use_cache` and
+    both `events.pt` and `max_refractory_period.pt` present they are read and neither the raw file nor the library is
+    touched; otherwise the table is built on the device (`build_event_table`) and, with `use_cache`, both caches are
+    written in the forms `load_events` / `load_max_refractory_period` read (a cache file that exists is used as it is and
+    not replaced).  The permutation is `load_events`' own, applied as a gather on the device."""
+    cache, tau_path = os.path.join(root, TF_EVENTS), os.path.join(root, MAX_REFRACTORY_PERIOD)
+    have_events, have_tau = (use_cache and os.path.isfile(p) for p in (cache, tau_path))
+    if have_events and have_tau:
+        events, tau_max = dict(torch.load(cache)), torch.load(tau_path)
+    else:
+        calib = np.load(os.path.join(root, CAMERA_CALIBRATION))
+        raw = np.load(os.path.join(root, RAW_EVENTS))
+        events, tau_max = build_event_table(raw["position"], raw["timestamp"], raw["polarity"], calib, device)
+        if have_events:
+            events = dict(torch.load(cache))
+        elif use_cache:
+            torch.save({k: v.cpu() for k, v in events.items()}, cache)
+        if have_tau:
+            tau_max = torch.load(tau_path)
+        elif use_cache:
+            torch.save(tau_max, tau_path)
+    events = {k: v.to(device) for k, v in events.items()}
+    if permutation_seed is not None:                       # tensor_ops.randperm_manual_seed
+        perm = torch.randperm(len(events["position"]), generator=torch.Generator().manual_seed(permutation_seed)).to(device)
+        events = {k: v[perm] for k, v in events.items()}
+    return events, tau_max
+
+
 def load_camera_poses(root: str):
     """camera_poses.npz -> (T_wc_timestamp i64 (C,), T_wc_position f32 (C,3), T_wc_orientation XYZW f32 (C,4))."""
     z = np.load(os.path.join(root, CAMERA_POSES))

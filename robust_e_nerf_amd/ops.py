@@ -725,6 +725,71 @@ def event_frame_compare(counts: torch.Tensor, pred: torch.Tensor, valid: torch.T
     return out
 
 
+# ------------------------------------------------------------------------------- event table
+EVENT_TABLE_THREADS = 256            # REN_EVENT_TABLE_THREADS: workgroup size of both kernels
+EVENT_TABLE_MAX_N = 2 ** 31 - 1      # N and H * W stay below 2^31
+INT64_MAX = 2 ** 63 - 1
+_POSITION_BYTES = {torch.uint16: 2, torch.int32: 4, torch.int64: 8}
+
+
+def event_intervals(pix_sorted: torch.Tensor, order: torch.Tensor, timestamp: torch.Tensor):
+    """pix_sorted (N,) int32 pixel keys in stable by-pixel order, order (N,) int64 as `torch.sort(stable=True)` returns it,
+    timestamp (N,) int64 in stream order -> valid (N,) uint8 and start_ts (N,) int64 in stream order (start_ts is written
+    where valid only) and min_diff (1,) int64: the smallest kept interval, INT64_MAX when none is kept.  An event is kept when
+    the slot before it in the by-pixel order holds the same pixel at a different time (data.queue_raw_events)."""
+    n = timestamp.shape[0]
+    if pix_sorted.shape != (n,) or order.shape != (n,):
+        raise ValueError(f"event_intervals: pix_sorted / order must be ({n},); got {tuple(pix_sorted.shape)}, {tuple(order.shape)}")
+    dev = timestamp.device
+    valid = torch.empty(n, device=dev, dtype=torch.uint8)
+    start_ts = torch.empty(n, device=dev, dtype=torch.int64)
+    min_diff = torch.full((1,), INT64_MAX, device=dev, dtype=torch.int64)
+    if n == 0:
+        return valid, start_ts, min_diff
+    check(_lib.load().ren_event_intervals(_ptr(pix_sorted, torch.int32), _ptr(order, torch.int64), _ptr(timestamp, torch.int64), n,
+                                          _ptr(valid), _ptr(start_ts), _ptr(min_diff), _stream()), "ren_event_intervals")
+    return valid, start_ts, min_diff
+
+
+def event_table_write(valid: torch.Tensor, offsets: torch.Tensor, position: torch.Tensor, timestamp: torch.Tensor,
+                      start_ts: torch.Tensor, polarity: torch.Tensor, m: int, height: int, width: int,
+                      lut: Optional[torch.Tensor] = None, bayer_channels: Optional[Sequence[int]] = None):
+    """the kept events (valid (N,) uint8, offsets (N,) int32 = its exclusive prefix sum, m = its sum) compacted in stream
+    order into the training table: position (m, 2) float32 -- `lut` (H * W, 2) float32 gathered at the event's pixel, or the
+    stored coordinates cast -- start_ts / end_ts / num_pos / num_neg (m,) int64 and, with `bayer_channels` (the channel of the
+    tile positions TL, TR, BL, BR), channel_idx (m,) uint8.  position: (N, 2) uint16 / int32 / int64 as stored, polarity: (N,)
+    bool / uint8.  The CALLER has checked 0 <= x < width and 0 <= y < height (data.build_event_table)."""
+    n = timestamp.shape[0]
+    m = int(m)
+    if position.shape != (n, 2) or position.dtype not in _POSITION_BYTES:
+        raise ValueError(f"event_table_write: position must be ({n}, 2) uint16 / int32 / int64; got {position.dtype} {tuple(position.shape)}")
+    if polarity.shape != (n,) or polarity.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"event_table_write: polarity must be ({n},) bool / uint8; got {polarity.dtype} {tuple(polarity.shape)}")
+    if valid.shape != (n,) or offsets.shape != (n,) or start_ts.shape != (n,) or not 0 <= m <= n:
+        raise ValueError(f"event_table_write: valid / offsets / start_ts must be ({n},) and 0 <= m <= {n}")
+    if lut is not None and lut.shape != (height * width, 2):
+        raise ValueError(f"event_table_write: lut must be ({height * width}, 2); got {tuple(lut.shape)}")
+    if bayer_channels is not None and len(bayer_channels) != 4:
+        raise ValueError("event_table_write: bayer_channels holds the channel of the four tile positions")
+    dev = timestamp.device
+    out = {"position": torch.empty(m, 2, device=dev, dtype=torch.float32)}
+    for k in ("start_ts", "end_ts", "num_pos", "num_neg"):
+        out[k] = torch.empty(m, device=dev, dtype=torch.int64)
+    code = None
+    if bayer_channels is not None:
+        out["channel_idx"] = torch.empty(m, device=dev, dtype=torch.uint8)
+        code = (ctypes.c_uint8 * 4)(*(int(c) for c in bayer_channels))
+    if n == 0 or m == 0:
+        return out
+    check(_lib.load().ren_event_table_write(
+        _ptr(valid, torch.uint8), _ptr(offsets, torch.int32), _ptr(position), _POSITION_BYTES[position.dtype],
+        _ptr(timestamp, torch.int64), _ptr(start_ts, torch.int64), _ptr(polarity), n, m, _ptr(lut, torch.float32), height, width,
+        None if code is None else ctypes.cast(code, ctypes.c_void_p), _ptr(out["position"]), _ptr(out["start_ts"]),
+        _ptr(out["end_ts"]), _ptr(out["num_pos"]), _ptr(out["num_neg"]), _ptr(out.get("channel_idx")), _stream()),
+        "ren_event_table_write")
+    return out
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 

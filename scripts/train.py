@@ -71,12 +71,13 @@ def main():
         pos_ct, neg_ct, tau0, tau_max = 0.25, 0.25, 0.0, torch.tensor(1e5, dtype=torch.float64)
     else:
         root = args.dataset_dir or dcfg["dataset_directory"]
-        events = data.load_events(root, dcfg.get("train_dataset_perm_seed"), device=dev)
+        # the event table is built (or read from its caches) on the device together with tau_max: one sort, two launches
+        events, tau_max = data.load_event_table(root, dcfg.get("train_dataset_perm_seed"), device=dev)
+        tau_max = tau_max.to(torch.float64)
         tab_ts, tab_pos, tab_quat = data.load_camera_poses(root)
         calib = data.load_calibration(root)
         Kinv = calib["Kinv"]
         pos_ct, neg_ct = float(calib["pos_contrast_threshold"]), float(calib["neg_contrast_threshold"])
-        tau_max = data.load_max_refractory_period(root).to(torch.float64)
         tau0 = float(calib["refractory_period"])
         if not (0 <= tau0 < float(tau_max)):               # event_generation_params.py:89,113-130
             import warnings

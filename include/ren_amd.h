@@ -842,6 +842,44 @@ int ren_event_table_write(const uint8_t *valid, const int32_t *offsets, const vo
                           int64_t *out_start_ts, int64_t *out_end_ts, int64_t *out_num_pos, int64_t *out_num_neg,
                           uint8_t *out_channel_idx, void *stream);
 
+/* ---- mesh (csrc/ren_mesh.hip) ------------------------------------------------------------------------- *
+ * Triangle mesh of the level set sigma = level of a regular lattice of densities, by marching tetrahedra.  Everything below is
+ * fixed by the lattice, so the output is the same index for index on every run and can be restated on the CPU.
+ * Lattice: nx x ny x nz points (each >= 2, at most 2^30 in all) over the box [lo, hi]; point (i, j, k) at the linear index
+ * (i * ny + j) * nz + k carries a float32 sigma and is INSIDE when sigma >= level (NaN outside, +inf inside, -inf outside).
+ * Tetrahedra: every cube is cut into the six tetrahedra of the Freudenthal / Kuhn split, v0 = base, v1 = v0 + e_a, v2 = v1 + e_b,
+ * v3 = v2 + e_c for the permutations (a, b, c) of the axes in lexicographic order (tetrahedron number 0 .. 5); they share the
+ * body diagonal, and the split is the same in every cube, so neighbours agree on their face diagonals.
+ * Edges: every tetrahedron edge leaves a lattice point p in one of seven directions e = 0 .. 6: (1,0,0), (0,1,0), (0,0,1),
+ * (1,1,0), (1,0,1), (0,1,1), (1,1,1); p OWNS (p, e).  An edge whose far end lies outside the lattice does not exist.
+ * Vertices: one on every existing edge whose ends differ in inside / outside, computed by the owner in float32, every operation
+ * rounded on its own:  t = (level - sigma_p) / (sigma_q - sigma_p), replaced by 0.5 when not finite;
+ * u = (float(i) + t di, float(j) + t dj, float(k) + t dk);  x = min(lo + u h, hi) per axis, h = (hi - lo) / (n - 1) computed by
+ * the caller in float64 and passed as float32 (the min: the rounding of h can carry the last lattice plane an ulp past hi).
+ * Vertex order: ascending lattice index, then e: id(p, e) = voff[p] + popcount(mask[p] & ((1 << e) - 1)), mask[p] = the 7-bit set
+ * of crossed edges p owns, voff = the exclusive prefix sum of popcount(mask).
+ * Triangles of a tetrahedron, corners named by its edges: one inside vertex a -> the edges to the three outside vertices in
+ * ascending order of (v0 .. v3); three inside -> the edges from the outside vertex likewise; two inside a < b and two outside
+ * c < d -> (ac, ad, bd) and (ac, bd, bc).  Orientation is COMBINATORIAL: the last two corners are swapped where the listed order
+ * would point from the outside vertices to the inside ones, decided from the inside set and the parity of (a, b, c), never from
+ * the computed positions; the normal points along -grad sigma.  Triangles of zero area (sigma == level at lattice points) are
+ * kept and pair with their neighbours.  Face order: ascending cube index (i * (ny-1) + j) * (nz-1) + k, then tetrahedron, then
+ * triangle.
+ * ren_mesh_classify: sigma (nx*ny*nz float32) -> mask (uint8 per point), vcount (int32 per point, popcount of mask), fcount
+ * (int32 per CUBE, (nx-1)(ny-1)(nz-1) entries at the cube index: 0 .. 12 triangles).  One launch.
+ * ren_mesh_write: with voff / foff the exclusive prefix sums (int64, ren_exclusive_scan) of vcount / fcount and V / F their
+ * totals: verts (V, 3) float32 and faces (F, 3) int32.  lo, hi, h: 3 floats each on the HOST.  One launch; a row at or beyond V
+ * / F is not written.  V == 0 and F == 0 launches nothing.  No LDS, no atomics, no stack memory.
+ * REN_ERR_BAD_ARG before any launch for an extent below 2, more than 2^30 points, a NaN level, a null or misaligned pointer
+ * (verts / faces may be null when V / F is 0), V >= 2^31, V or F < 0, lo >= hi or h <= 0 on an axis, a box that is not finite. */
+#define REN_MESH_THREADS 256                 /* workgroup size of both kernels: one lattice point per lane */
+#define REN_MESH_MAX_POINTS (1 << 30)
+int ren_mesh_classify(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, uint8_t *mask, int32_t *vcount,
+                      int32_t *fcount, void *stream);
+int ren_mesh_write(const float *sigma, const uint8_t *mask, const int64_t *voff, const int64_t *foff, int32_t nx, int32_t ny,
+                   int32_t nz, float level, const float *lo, const float *hi, const float *h, int64_t V, int64_t F, float *verts,
+                   int32_t *faces, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

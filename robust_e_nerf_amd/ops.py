@@ -790,6 +790,65 @@ def event_table_write(valid: torch.Tensor, offsets: torch.Tensor, position: torc
     return out
 
 
+# ------------------------------------------------------------------------------- mesh (level set of a density lattice)
+MESH_MAX_POINTS = 2 ** 30            # include/ren_amd.h REN_MESH_MAX_POINTS
+MESH_MAX_VERTS = 2 ** 31             # the vertex total must stay below it: faces are int32
+
+
+def _mesh_lattice(sigma: torch.Tensor, level: float, what: str):
+    if sigma.dim() != 3 or min(sigma.shape) < 2:
+        raise ValueError(f"{what}: sigma must be (nx, ny, nz) with every extent >= 2; got {tuple(sigma.shape)}")
+    if sigma.shape[0] * sigma.shape[1] * sigma.shape[2] > MESH_MAX_POINTS:
+        raise ValueError(f"{what}: a lattice of {tuple(sigma.shape)} has more than 2^30 points")
+    if math.isnan(float(level)):
+        raise ValueError(f"{what}: level is NaN")
+    return tuple(int(s) for s in sigma.shape)
+
+
+def mesh_classify(sigma: torch.Tensor, level: float):
+    """sigma (nx, ny, nz) float32 -> mask (n,) uint8: the crossed edges each lattice point owns, vcount (n,) int32 = its
+    popcount, fcount ((nx-1)(ny-1)(nz-1),) int32: the triangles of each cube.  A point is inside when sigma >= level
+    (include/ren_amd.h "mesh")."""
+    nx, ny, nz = _mesh_lattice(sigma, level, "mesh_classify")
+    ps = _ptr(sigma, torch.float32)
+    dev = sigma.device
+    n = nx * ny * nz
+    mask = torch.empty(n, device=dev, dtype=torch.uint8)
+    vcount = torch.empty(n, device=dev, dtype=torch.int32)
+    fcount = torch.empty((nx - 1) * (ny - 1) * (nz - 1), device=dev, dtype=torch.int32)
+    check(_lib.load().ren_mesh_classify(ps, nx, ny, nz, _f(level), _ptr(mask), _ptr(vcount), _ptr(fcount), _stream()),
+          "ren_mesh_classify")
+    return mask, vcount, fcount
+
+
+def mesh_write(sigma: torch.Tensor, level: float, mask: torch.Tensor, voff: torch.Tensor, foff: torch.Tensor, lo: Sequence[float],
+               hi: Sequence[float], n_verts: int, n_faces: int):
+    """-> verts (n_verts, 3) float32, faces (n_faces, 3) int32 from mesh_classify's mask and the exclusive prefix sums voff /
+    foff (int64, exclusive_scan) of its vcount / fcount, whose totals are n_verts / n_faces.  lo, hi: the world box of the
+    lattice; the spacing (hi - lo) / (n - 1) is formed here in float64 and passed as float32.  Zero totals launch nothing."""
+    nx, ny, nz = _mesh_lattice(sigma, level, "mesh_write")
+    n, cubes = nx * ny * nz, (nx - 1) * (ny - 1) * (nz - 1)
+    n_verts, n_faces = int(n_verts), int(n_faces)
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"mesh_write: the box needs finite lo < hi on every axis; got {lo}, {hi}")
+    if mask.shape != (n,) or voff.shape != (n,) or foff.shape != (cubes,):
+        raise ValueError(f"mesh_write: mask / voff must be ({n},) and foff ({cubes},)")
+    if not 0 <= n_verts < MESH_MAX_VERTS or n_faces < 0:
+        raise ValueError(f"mesh_write: {n_verts} vertices: the total must stay below 2^31")
+    ptrs = (_ptr(sigma, torch.float32), _ptr(mask, torch.uint8), _ptr(voff, torch.int64), _ptr(foff, torch.int64))
+    dev = sigma.device
+    verts = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_faces, 3, device=dev, dtype=torch.int32)
+    if n_verts == 0 and n_faces == 0:
+        return verts, faces
+    f3 = ctypes.c_float * 3
+    h = [(b - a) / (r - 1) for a, b, r in zip(lo, hi, (nx, ny, nz))]
+    check(_lib.load().ren_mesh_write(*ptrs, nx, ny, nz, _f(level), f3(*lo), f3(*hi), f3(*h), n_verts, n_faces, _ptr(verts),
+                                     _ptr(faces), _stream()), "ren_mesh_write")
+    return verts, faces
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 

@@ -1,0 +1,79 @@
+"""Export the density level set of a checkpoint as a triangle mesh (binary PLY, per-vertex normals for arch ngp).
+
+    python scripts/export_mesh.py --config <YAML> --ckpt runs/train/last.ckpt --out mesh.ply \
+        [--resolution N | --resolution NX NY NZ] [--level L] [--aabb x0 y0 z0 x1 y1 z1] [--no-normals]
+
+The field is loaded as scripts/render.py loads it.  The density is sampled on a regular lattice of --resolution points per
+axis over --aabb (default: the model's box), the surface sigma = --level is extracted on the GPU (robust_e_nerf_amd/mesh.py)
+and every vertex gets the direction of -grad sigma as its normal, the convention of `render.py --normals`.  Arch mlp has no
+density gradient: its mesh is written without normals.  `model.nerf.aabb: auto` spans the camera positions, so it needs
+--dataset-dir, --synthetic or an explicit --aabb.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--ckpt", help="checkpoint to load (default: the YAML's model.checkpoint_filepath)")
+    ap.add_argument("--out", required=True, help="the PLY file to write")
+    ap.add_argument("--resolution", type=int, nargs="+", default=[256],
+                    help="lattice points per axis: one value for all three axes or NX NY NZ (default 256)")
+    ap.add_argument("--level", type=float, default=10.0,
+                    help="density of the extracted surface (default 10.0: a parameter for the user to choose per scene, not a "
+                         "value measured on any field)")
+    ap.add_argument("--aabb", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="world box of the lattice (default: the model's box)")
+    ap.add_argument("--no-normals", action="store_true", help="write the mesh without per-vertex normals")
+    ap.add_argument("--dataset-dir", help="camera poses for `aabb: auto` (default: the YAML's data.dataset_directory)")
+    ap.add_argument("--synthetic", action="store_true", help="`aabb: auto` from the synthetic benchmark orbit")
+    args = ap.parse_args(argv)
+    if len(args.resolution) not in (1, 3):
+        ap.error("--resolution takes one value or three")
+    args.resolution = tuple(args.resolution * 3 if len(args.resolution) == 1 else args.resolution)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from robust_e_nerf_amd import checkpoint, config, data, mesh
+    from render import load_config
+    cfg, ckpt = load_config(args.config, args.ckpt)
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    ncfg = cfg["model"]["nerf"]
+    tab_pos = None
+    if ncfg["aabb"] == "auto":
+        if args.synthetic:
+            import bench
+            tab_pos = torch.from_numpy(bench.synthetic_scene()[1])
+        else:
+            tab_pos = data.load_camera_poses(args.dataset_dir or cfg["data"]["dataset_directory"])[1]
+    rcfg = config.render_cfg(cfg, tab_pos)
+    sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
+    arch = ncfg.get("arch", "ngp")
+    fld, r = config.make_renderer(ncfg, rcfg, checkpoint.radiance_dim(sd, arch), dev)
+    checkpoint.load_render_state(sd, fld, r, arch)
+    normals = not args.no_normals
+    if normals and arch != "ngp":
+        print(f"arch {arch} has no density gradient: the mesh is written without normals", flush=True)
+        normals = False
+    lo, hi = (args.aabb[:3], args.aabb[3:]) if args.aabb else (None, None)
+    t0 = time.perf_counter()
+    stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"{stats['verts']} vertices, {stats['faces']} faces ({'with' if normals else 'no'} normals) at resolution "
+          f"{' x '.join(str(v) for v in stats['resolution'])}, level {args.level:g}: {args.out} written in {dt:.2f} s", flush=True)
+
+
+if __name__ == "__main__":
+    main()

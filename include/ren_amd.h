@@ -880,6 +880,33 @@ int ren_mesh_write(const float *sigma, const uint8_t *mask, const int64_t *voff,
                    int32_t nz, float level, const float *lo, const float *hi, const float *h, int64_t V, int64_t F, float *verts,
                    int32_t *faces, void *stream);
 
+/* ---- mesh components (csrc/ren_mesh_components.hip) ---------------------------------------------------- *
+ * Connected components of the lattice of "mesh": its solids (floaters among them) and, with outside != 0, its voids (cavities
+ * among them).  Lattice, linear index p = (i * ny + j) * nz + k and INSIDE (sigma >= level; NaN outside) as in "mesh".
+ * Selected set S: the inside points; with outside != 0 the complement, NaN points included.
+ * Neighbours of p: p + e and p - e for the seven directions e of "mesh", (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1),
+ * (1,1,1), where that point lies in the lattice: the ends of the marching-tetrahedra edges at p.  The other six diagonal pairs of
+ * the 26-neighbourhood, (1,-1,0) for one, are NOT neighbours.  The same neighbourhood holds for S and for its complement: both
+ * sides of the surface are connected along tetrahedron edges.
+ * Component: an equivalence class of S under "joined by a chain of neighbours in S".
+ * label[p] (int32, n = nx*ny*nz entries) = the smallest linear index of p's component, -1 for p not in S;
+ * size[r] (int32, n entries) = the number of points of the component whose smallest index is r, 0 where r is no such root;
+ * border[r] (uint8, n entries) = 1 when that component has a point on a face of the lattice (i in {0, nx-1}, or j, or k
+ * likewise), else 0; 0 where r is no root.
+ * All three are functions of (sigma, level, outside) alone: the result repeats bit for bit.
+ * ren_mesh_components: three launches whatever the data (init; union by compare-and-swap of the larger root under the smaller,
+ * every access to label a relaxed atomic of agent scope; flatten + count), no host read, no scratch beyond the outputs: label is
+ * the parent array, size and border are cleared by the call.  No loop waits for another wave or workgroup.
+ * ren_mesh_component_apply: one launch; out[p] = value where label[p] >= 0 and drop[label[p]] != 0 (drop: n uint8, indexed by
+ * root), else the 32 bits of sigma[p] unchanged (NaN payloads survive).  out may alias sigma.  A label that is no index of the
+ * n points drops nothing.  n == 0 launches nothing.
+ * REN_ERR_BAD_ARG before any launch for an extent below 2, more than REN_MESH_MAX_POINTS points, a NaN level, a null pointer or
+ * one not aligned to its element, n < 0, outside other than 0 or 1, a NaN value. */
+int ren_mesh_components(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float level, int32_t outside, int32_t *label,
+                        int32_t *size, uint8_t *border, void *stream);
+int ren_mesh_component_apply(const float *sigma, const int32_t *label, const uint8_t *drop, int64_t n, float value, float *out,
+                             void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

@@ -163,6 +163,8 @@ SIGNATURES = {
     "ren_mesh_classify": (c_int, [P, c_int32, c_int32, c_int32, c_float, P, P, P, P]),
     "ren_mesh_write": (c_int, [P, P, P, P, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                c_int64, c_int64, P, P, P]),
+    "ren_mesh_components": (c_int, [P, c_int32, c_int32, c_int32, c_float, c_int32, P, P, P, P]),
+    "ren_mesh_component_apply": (c_int, [P, P, P, c_int64, c_float, P, P]),
 }
 
 _lib = None

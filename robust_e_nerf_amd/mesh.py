@@ -9,6 +9,10 @@ ops.exclusive_scan, ops.mesh_write -- include/ren_amd.h "mesh" fixes every index
 vertices get the direction of -grad sigma as their normal (`vertex_normals`, through `Renderer.density_gradient`: arch ngp),
 the convention of the normal maps.  Triangles of zero area (sigma == level exactly at lattice points) are kept; the caller may
 drop them.  The whole lattice lives in device memory at once.
+
+`clean` (export's min_points / largest / fill_cavities) rewrites the lattice before the extraction: floaters -- small connected
+components of the inside points -- are dropped and cavities -- outside components that reach no face of the lattice -- are
+filled, with the components labelled on the GPU (`components`: ops.mesh_components, include/ren_amd.h "mesh components").
 """
 from __future__ import annotations
 
@@ -86,6 +90,72 @@ def extract(sigma: torch.Tensor, level: float, lo: Sequence[float], hi: Sequence
     return ops.mesh_write(sigma, level, mask, voff, foff, lo, hi, n_verts, n_faces)
 
 
+def components(sigma: torch.Tensor, level: float, outside: bool = False):
+    """connected components of the inside points (sigma >= level; with `outside` of their complement, NaN included) under the
+    marching-tetrahedra edges (include/ren_amd.h "mesh components") -> label (nx, ny, nz) int32: the smallest linear index of
+    the point's component, -1 where not selected; roots (C,) int64 ascending: those smallest indices; sizes (C,) int32: the
+    points of each; border (C,) uint8: 1 where the component touches a face of the lattice.  One host synchronisation (C)."""
+    label, size, border = ops.mesh_components(sigma, level, outside)
+    roots = torch.nonzero(size).reshape(-1)
+    return label, roots, size[roots], border[roots]
+
+
+def _rule(min_points, largest):
+    if int(min_points) != min_points or min_points < 1 or (largest is not None and (int(largest) != largest or largest < 1)):
+        raise ValueError(f"mesh: min_points and largest are integers >= 1 (largest may be None); got {min_points}, {largest}")
+
+
+def kept_components(sizes: torch.Tensor, min_points: int = 1, largest: Optional[int] = None) -> torch.Tensor:
+    """`clean`'s rule on the sizes of the components in ascending order of their roots -> bool per component: kept iff
+    size >= min_points and (largest is None or rank < largest), the rank by (size descending, root ascending)"""
+    _rule(min_points, largest)
+    keep = sizes >= min_points
+    if largest is not None:
+        order = torch.argsort(sizes, descending=True, stable=True)               # stable: a tie goes to the smaller root
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel(), device=order.device)
+        keep = keep & (rank < largest)
+    return keep
+
+
+def _mark(n: int, roots: torch.Tensor) -> torch.Tensor:
+    drop = torch.zeros(n, device=roots.device, dtype=torch.uint8)
+    drop[roots] = 1
+    return drop
+
+
+def clean(sigma: torch.Tensor, level: float, min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False):
+    """sigma (nx, ny, nz) float32 -> (sigma', stats): the lattice without its floaters and, with `fill_cavities`, without its
+    cavities, for the unchanged `extract`.
+    1. Drop.  The inside components are ranked by (size descending, root ascending); one is kept iff size >= min_points and
+       (largest is None or rank < largest); the points of the others become -inf.
+    2. Fill, if fill_cavities.  The outside components OF THE RESULT OF STEP 1 that touch no face of the lattice are cavities
+       (a dropped floater inside one is part of it by now); their points become +inf.
+    stats: components (inside, before), kept, dropped_points, cavities, filled_points.  Nothing to drop or fill returns the
+    input tensor itself.  ValueError for min_points < 1, largest < 1 or a level that is not finite.
+    Why +-inf is safe and `extract` needs no change: a component is maximal, so every neighbour of a dropped point is outside
+    or dropped with it, and every neighbour of a filled point is inside.  No marching-tetrahedra edge at a rewritten point is
+    crossed, no interpolation ever reads the +-inf, and every surviving vertex lies on an edge whose two sigma values are
+    untouched: the vertices of extract(clean(sigma)) are, bit for bit, a subset of those of extract(sigma)."""
+    _rule(min_points, largest)
+    if not math.isfinite(float(level)):
+        raise ValueError(f"mesh.clean: the level must be finite (a rewritten point is +-inf); got {level}")
+    n = sigma.numel()
+    label, roots, sizes, _ = components(sigma, level)
+    keep = kept_components(sizes, min_points, largest)
+    stats = dict(components=int(roots.numel()), kept=int(keep.sum()), dropped_points=int(sizes[~keep].sum()), cavities=0,
+                 filled_points=0)
+    if stats["kept"] < stats["components"]:
+        sigma = ops.mesh_component_apply(sigma, label, _mark(n, roots[~keep]), -math.inf)
+    if fill_cavities:
+        label, roots, sizes, border = components(sigma, level, outside=True)
+        closed = border == 0
+        stats.update(cavities=int(closed.sum()), filled_points=int(sizes[closed].sum()))
+        if stats["cavities"]:
+            sigma = ops.mesh_component_apply(sigma, label, _mark(n, roots[closed]), math.inf)
+    return sigma, stats
+
+
 def vertex_normals(r, verts: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
     """(V, 3) float32: -grad sigma / |grad sigma| at the vertices (r.density_gradient: arch ngp; arch mlp raises
     NotImplementedError); a zero gradient gives a zero normal"""
@@ -122,9 +192,11 @@ def write_ply(path: str, verts, faces, normals=None) -> None:
 
 
 def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None,
-           normals: bool = True) -> dict:
-    """sample, extract, (normals,) write `path`; the box defaults to the renderer's cfg.aabb.
-    -> dict(verts=V, faces=F, resolution=(nx, ny, nz), normals=bool)"""
+           normals: bool = True, min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False) -> dict:
+    """sample, (clean,) extract, (normals,) write `path`; the box defaults to the renderer's cfg.aabb.
+    -> dict(verts=V, faces=F, resolution=(nx, ny, nz), normals=bool); with min_points > 1, largest or fill_cavities the lattice
+    goes through `clean` first and the dict carries its stats as well"""
+    _rule(min_points, largest)
     aabb = [float(v) for v in r.cfg.aabb]
     lo = aabb[:3] if lo is None else lo
     hi = aabb[3:] if hi is None else hi
@@ -132,8 +204,11 @@ def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] =
     if math.isnan(float(level)):
         raise ValueError("mesh.export: level is NaN")
     sigma = sample_density(r, lo, hi, res)
+    cleaned = {}
+    if min_points > 1 or largest is not None or fill_cavities:
+        sigma, cleaned = clean(sigma, level, min_points, largest, fill_cavities)
     verts, faces = extract(sigma, level, lo, hi)
     del sigma
     nrm = vertex_normals(r, verts) if normals else None
     write_ply(path, verts, faces, nrm)
-    return dict(verts=int(verts.shape[0]), faces=int(faces.shape[0]), resolution=res, normals=bool(normals))
+    return dict(verts=int(verts.shape[0]), faces=int(faces.shape[0]), resolution=res, normals=bool(normals), **cleaned)

@@ -849,6 +849,45 @@ def mesh_write(sigma: torch.Tensor, level: float, mask: torch.Tensor, voff: torc
     return verts, faces
 
 
+def mesh_components(sigma: torch.Tensor, level: float, outside: bool = False):
+    """sigma (nx, ny, nz) float32 -> label (nx, ny, nz) int32: the smallest linear index of the point's connected component
+    under the marching-tetrahedra edges, -1 for a point that is not selected; size (n,) int32: the points of the component
+    rooted there, 0 elsewhere; border (n,) uint8: 1 at the root of a component that touches a face of the lattice.  Selected
+    are the inside points (sigma >= level), with `outside` their complement (include/ren_amd.h "mesh components")."""
+    nx, ny, nz = _mesh_lattice(sigma, level, "mesh_components")
+    ps = _ptr(sigma, torch.float32)
+    dev = sigma.device
+    n = nx * ny * nz
+    label = torch.empty(nx, ny, nz, device=dev, dtype=torch.int32)
+    size = torch.empty(n, device=dev, dtype=torch.int32)
+    border = torch.empty(n, device=dev, dtype=torch.uint8)
+    check(_lib.load().ren_mesh_components(ps, nx, ny, nz, _f(level), 1 if outside else 0, _ptr(label), _ptr(size), _ptr(border),
+                                          _stream()), "ren_mesh_components")
+    return label, size, border
+
+
+def mesh_component_apply(sigma: torch.Tensor, label: torch.Tensor, drop: torch.Tensor, value: float,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> a tensor like sigma (float32, any shape): `value` where the point's component is marked (label >= 0 and
+    drop[label] != 0; label int32 of sigma's shape, drop (n,) uint8 indexed by root), the bits of sigma elsewhere.  `out`:
+    where to write instead of a new tensor; it may be sigma itself."""
+    n = sigma.numel()
+    if label.shape != sigma.shape or drop.shape != (n,):
+        raise ValueError(f"mesh_component_apply: label must be {tuple(sigma.shape)} and drop ({n},)")
+    if out is not None and out.shape != sigma.shape:
+        raise ValueError(f"mesh_component_apply: out must be {tuple(sigma.shape)}")
+    if n > MESH_MAX_POINTS:
+        raise ValueError(f"mesh_component_apply: {n} points are more than 2^30")
+    if math.isnan(float(value)):
+        raise ValueError("mesh_component_apply: value is NaN")
+    ptrs = (_ptr(sigma, torch.float32), _ptr(label, torch.int32), _ptr(drop, torch.uint8))
+    if out is None:
+        out = torch.empty_like(sigma)
+    check(_lib.load().ren_mesh_component_apply(*ptrs, n, _f(value), _ptr(out, torch.float32), _stream()),
+          "ren_mesh_component_apply")
+    return out
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 

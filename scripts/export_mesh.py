@@ -2,11 +2,13 @@
 
     python scripts/export_mesh.py --config <YAML> --ckpt runs/train/last.ckpt --out mesh.ply \
         [--resolution N | --resolution NX NY NZ] [--level L] [--aabb x0 y0 z0 x1 y1 z1] [--no-normals]
+        [--min-component N] [--largest K] [--fill-cavities]
 
 The field is loaded as scripts/render.py loads it.  The density is sampled on a regular lattice of --resolution points per
 axis over --aabb (default: the model's box), the surface sigma = --level is extracted on the GPU (robust_e_nerf_amd/mesh.py)
 and every vertex gets the direction of -grad sigma as its normal, the convention of `render.py --normals`.  Arch mlp has no
-density gradient: its mesh is written without normals.  `model.nerf.aabb: auto` spans the camera positions, so it needs
+density gradient: its mesh is written without normals.  --min-component / --largest drop floaters (connected pieces of the
+solid, counted in lattice points) and --fill-cavities closes the voids inside objects before the extraction (mesh.clean).  `model.nerf.aabb: auto` spans the camera positions, so it needs
 --dataset-dir, --synthetic or an explicit --aabb.
 """
 import argparse
@@ -33,11 +35,18 @@ def parse_args(argv=None):
     ap.add_argument("--aabb", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                     help="world box of the lattice (default: the model's box)")
     ap.add_argument("--no-normals", action="store_true", help="write the mesh without per-vertex normals")
+    ap.add_argument("--min-component", type=int, default=1, metavar="N",
+                    help="drop the connected pieces of the solid with fewer than N lattice points: floaters (default 1: keep all)")
+    ap.add_argument("--largest", type=int, metavar="K", help="keep only the K largest connected pieces of the solid")
+    ap.add_argument("--fill-cavities", action="store_true",
+                    help="fill the voids that reach no face of the lattice: no inner surface of a hollow object")
     ap.add_argument("--dataset-dir", help="camera poses for `aabb: auto` (default: the YAML's data.dataset_directory)")
     ap.add_argument("--synthetic", action="store_true", help="`aabb: auto` from the synthetic benchmark orbit")
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one value or three")
+    if args.min_component < 1 or (args.largest is not None and args.largest < 1):
+        ap.error("--min-component and --largest take integers >= 1")
     args.resolution = tuple(args.resolution * 3 if len(args.resolution) == 1 else args.resolution)
     return args
 
@@ -68,11 +77,15 @@ def main(argv=None):
         normals = False
     lo, hi = (args.aabb[:3], args.aabb[3:]) if args.aabb else (None, None)
     t0 = time.perf_counter()
-    stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals)
+    stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals, min_points=args.min_component,
+                        largest=args.largest, fill_cavities=args.fill_cavities)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{stats['verts']} vertices, {stats['faces']} faces ({'with' if normals else 'no'} normals) at resolution "
           f"{' x '.join(str(v) for v in stats['resolution'])}, level {args.level:g}: {args.out} written in {dt:.2f} s", flush=True)
+    if "components" in stats:
+        print(f"{stats['components']} connected pieces, {stats['kept']} kept ({stats['dropped_points']} lattice points dropped); "
+              f"{stats['cavities']} cavities filled ({stats['filled_points']} lattice points)", flush=True)
 
 
 if __name__ == "__main__":

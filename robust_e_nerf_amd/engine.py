@@ -14,13 +14,13 @@ import math
 from dataclasses import dataclass, field as dc_field
 from typing import Dict, Optional, Sequence, Tuple
 
-import contextlib
 import dataclasses
 import os
 import threading
 import torch
 
 from . import ops
+from .fronts import DiffFront, GradFront, StepFronts
 from .step_graph import StepGraphs
 
 
@@ -218,22 +218,6 @@ def pack_batch(batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         out[k] = view
     out["_pack"] = buf
     return out
-
-
-def _adopt(v, stream):
-    """tensors allocated on another stream's pool that `stream` is about to use (after waiting for their producer): tell the
-    caching allocator, so that their memory is not handed out again before `stream` is done with them"""
-    if isinstance(v, torch.Tensor):
-        if v.is_cuda:
-            v.record_stream(stream)
-    elif isinstance(v, dict):
-        for x in v.values():
-            _adopt(x, stream)
-    elif isinstance(v, (tuple, list)):
-        for x in v:
-            _adopt(x, stream)
-    elif isinstance(v, Packed):
-        _adopt((v.ray_indices, v.t_starts, v.t_ends, v.offsets, v.counts, v.feat, v.n_dev), stream)
 
 
 class CountLog:
@@ -960,12 +944,10 @@ class Trainer:
         self.world_size = world_size
         self.pg = process_group
         self.sync = None
-        self._side, self._prefetched, self._n_host = None, None, None   # Trainer.prefetch
-        self._ready_ev = None                                    # start of the last forward_backward() on its stream (early sampling)
+        self.fronts = StepFronts()                               # side stream, prefetch / begin_grad_sampling state
         self.early_grad_sampling = True                          # Trainer.step: third render's samples beside the l_diff backward
         self.grad_sampling: Optional[str] = None                 # "merged": that placement also for eager steps (grad_sampling_mode)
         self.side_cus = int(os.environ.get("REN_SIDE_CUS", 4))   # CUs the l_diff pass's MLP backward leaves to the side stream ("begun")
-        self._grad_begun, self._grad_pending, self._n_host_grad = None, None, None   # begin_grad_sampling
         if world_size > 1:
             from . import parallel
             self.sync = parallel.GradSync(process_group, world_size, compress=renderer.cfg.dp_compress)
@@ -1081,7 +1063,8 @@ class Trainer:
     def _repeat_with_host_counts(self, fn):
         """fn() again with host-side counts (the capacities learn from them), after a device-side count did not fit"""
         self.device_count_overflows += 1
-        self._dc_sync, self._grad_begun, self._grad_pending = True, None, None
+        self._dc_sync = True
+        self.fronts.reset()
         try:
             return fn()
         finally:
@@ -1136,7 +1119,7 @@ class Trainer:
         return p["ts"][:B], p["ts"][B:], p["target_diff"]
 
     # ---- the parameter-independent front of the l_diff step, and its prefetch ------------------------------------------
-    def _front(self, batch, jitter_start, jitter_end) -> dict:
+    def _front(self, batch, jitter_start, jitter_end) -> DiffFront:
         """event correction -> supervision timestamps -> poses -> rays of the start and end renders (a2-a6)"""
         t = self.t
         prep = ops.event_prepare(batch, 0.0, 0.0, 0.0, with_dtau=t.train_refractory_period, ep=self.ep)
@@ -1145,23 +1128,13 @@ class Trainer:
             # jitter_end None: jitter_start already holds the 2B uniforms of both renders (start rays first)
             jitter = jitter_start if jitter_end is None else torch.cat([jitter_start, jitter_end])
             jitter = jitter.to(torch.float32).contiguous()
-        front = dict(prep=prep, jitter=jitter)
-        if not t.train_refractory_period:
-            # poses + rays of both renders in one launch; the 2B timestamps share the B event pixels
-            front["o"], front["d"] = ops.pose_rays(prep["ts"], batch["position"].contiguous(), self.Kinv, self.tab_ts,
-                                                   self.tab_pos, self.tab_quat)
-        else:
-            front["px"] = torch.cat([batch["position"], batch["position"]]).contiguous()
-        return front
+        if t.train_refractory_period:
+            return DiffFront(prep, jitter, px=torch.cat([batch["position"], batch["position"]]).contiguous())
+        # poses + rays of both renders in one launch; the 2B timestamps share the B event pixels
+        o, d = ops.pose_rays(prep["ts"], batch["position"].contiguous(), self.Kinv, self.tab_ts, self.tab_pos, self.tab_quat)
+        return DiffFront(prep, jitter, o, d)
 
-    @property
-    def side_stream(self) -> "torch.cuda.Stream":
-        if self._side is None:
-            # normal priority (round 6; until then -1 = high): with a HIGH-priority stream in the process every other captured
-            # step replayed 25 % slower (small kernels of alternate captures took 45-55 us each: tools/recapture_probe.py,
-            # profiles/NOTES.md), and the eager lines and the e2e run are the same at either priority
-            self._side = torch.cuda.Stream(priority=int(os.environ.get("REN_SIDE_PRIORITY", 0)))
-        return self._side
+    side_stream = property(lambda self: self.fronts.side_stream)
 
     def prefetch(self, batch, jitter_start=None, jitter_end=None, next_global_step: Optional[int] = None) -> bool:
         """Run the front of the NEXT step's forward_backward(batch, jitter_start, jitter_end) -- event correction, poses,
@@ -1176,58 +1149,7 @@ class Trainer:
         16 steps) makes the early march stale: pass `next_global_step` so that it is not started before a refresh step;
         a stale one is recognised by the grid epoch and redone.  Otherwise this is a no-op and returns False.
         `batch` / the jitters must already be complete on the device or produced on `side_stream`."""
-        t = self.t
-        if t.train_contrast_threshold or t.train_refractory_period:
-            return False
-        if self.r.cfg.sampler != "uniform" and next_global_step is not None and next_global_step % self.r.cfg.occ_n == 0:
-            return False
-        side = self.side_stream
-        # Ordered AFTER the work already queued on this stream (round 4): run beside the persistent MLP backward kernels, the
-        # pose / ray kernels of this front produced a slightly wrong rotation for an aligned group of 16 rays in ~1 step out
-        # of 8 (same inputs, same kernel: tools/prefetch_diag2.py; packed-FP32 code beside matrix-core waves, profiles/NOTES.md:
-        # those files are now built without it, and this ordering stays as the second line of defence), which is what made
-        # test_prefetched_step_front_gives_the_same_steps fail in 40 % of its stand-alone runs.  What is left of the prefetch:
-        # the front shares the chip with the optimiser step only, and the host never enqueues it on the critical path.
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            front = self._front(batch, jitter_start, jitter_end)
-            st = self.r.sample_begin(front["o"], front["d"], front["jitter"], True)
-            if self._n_host is None:
-                self._n_host = torch.empty(1, dtype=st["total"].dtype).pin_memory()
-            self._n_host.copy_(st["total"].reshape(1), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        front["begun"] = st
-        self._prefetched = (self._prefetch_key(batch, jitter_start, jitter_end) + self._grid_state(), front, ev,
-                            (batch, jitter_start, jitter_end))
-        return True
-
-    def _grid_state(self):
-        """what the early march of the occupancy sampler read: the grid tensor's torch version and the refresh epoch"""
-        r = self.r
-        return (r.binary._version, getattr(r, "binary_epoch", 0), r.cfg.sampler)
-
-    @staticmethod
-    def _prefetch_key(batch, jitter_start, jitter_end):
-        """identity AND in-place version of every tensor the prefetched front was computed from: a batch or jitter tensor
-        mutated between prefetch() and forward_backward() (same object ids, new contents) must not reuse the stale front"""
-        ver = lambda t: (id(t), t._version) if isinstance(t, torch.Tensor) else (id(t), 0)
-        return (id(batch), tuple(sorted((k, ver(v)) for k, v in batch.items())), ver(jitter_start), ver(jitter_end))
-
-    def _take_prefetched(self, batch, jitter_start, jitter_end):
-        pf, self._prefetched = self._prefetched, None
-        t = self.t
-        if pf is None or pf[0] != self._prefetch_key(batch, jitter_start, jitter_end) + self._grid_state() or \
-                t.train_contrast_threshold or t.train_refractory_period:              # the guards of prefetch(), re-checked
-            return None
-        _, front, ev, _ = pf
-        ev.synchronize()                                               # host: waits for the side stream's few small kernels only
-        front["begun"]["n0"] = int(self._n_host[0])
-        cur = torch.cuda.current_stream()
-        cur.wait_event(ev)
-
-        _adopt(front, cur)                                             # side-stream allocations now used on this stream
-        return front
+        return self.fronts.prefetch(self, batch, jitter_start, jitter_end, next_global_step)
 
     def forward_backward(self, batch, jitter_start=None, jitter_end=None, final: Optional[bool] = None):
         """Loss + gradients (no optimiser step).  Returns (loss tensor (device scalar), aux).  final: this is the step's last
@@ -1239,15 +1161,8 @@ class Trainer:
     def _forward_backward(self, batch, jitter_start, jitter_end, final, dc):
         r, t, f = self.r, self.t, self.r.field
         B = batch["position"].shape[0]
-        if f.flat.is_cuda:
-            # everything enqueued so far (the last optimiser step, the occupancy-grid refresh, the batch) is what the sampling
-            # of this step's third render depends on: grad_loss_forward_backward(early=True) waits for this point only
-            self._ready_ev = torch.cuda.Event()
-            self._ready_ev.record()
-        front = self._take_prefetched(batch, jitter_start, jitter_end)
-        if front is None:
-            front = self._front(batch, jitter_start, jitter_end)
-        prep, px, jitter = front["prep"], front.get("px"), front["jitter"]
+        front = self.fronts.take_diff(self, batch, jitter_start, jitter_end)      # (prefetched, or made now)
+        prep, jitter = front.prep, front.jitter
         ts_all, target = prep["ts"], prep["target_diff"]
         bkgd = ops.bkgd_param_fwd(self.small, f.C) if t.bkgd_is_param else None              # nerf.py:81-88
         colords = None
@@ -1255,20 +1170,13 @@ class Trainer:
             # d loss/d tau needs dI/dt of both renders: carry the tangent forward (value path unchanged)
             from . import jvp
             pos, rot, dpos, drot = jvp.trajectory_jvp(ts_all, self.tab_ts, self.tab_pos, self.tab_quat)
-            o, d, od, dd = jvp.raygen_jvp(self.Kinv, px, pos, rot, dpos, drot)
-            begun = None
-            if self._grad_pending is not None:
-                begun = self._begin_with_grad(o, d, jitter, dc)
+            o, d, od, dd = jvp.raygen_jvp(self.Kinv, front.px, pos, rot, dpos, drot)
+            begun = self.fronts.begin_with_grad(self, front, o, d, dc)
             colors, colords, opac, ctx = jvp.render_forward(r, o, d, od, dd, jitter, bkgd, training=True, begun=begun,
                                                             device_counts=dc)
         else:
-            o, d = front["o"], front["d"]
-            if self._grad_pending is not None:
-                if front.get("begun") is None:
-                    front["begun"] = self._begin_with_grad(o, d, jitter, dc)
-                else:
-                    self._begin_grad_now()
-            colors, opac, depth, ctx = r.forward(o, d, jitter, bkgd, training=True, save=True, begun=front.get("begun"),
+            begun = self.fronts.begin_with_grad(self, front, front.o, front.d, dc)
+            colors, opac, depth, ctx = r.forward(front.o, front.d, jitter, bkgd, training=True, save=True, begun=begun,
                                                  device_counts=dc)
         # a16 + a18: intensity epilogue, validity, Bayer channel, loss and its gradient: two launches (ren_event_diff_loss_*)
         if f.C > 1 and "channel_idx" not in batch:
@@ -1325,7 +1233,7 @@ class Trainer:
             return "merged"
         return "begun"
 
-    def _grad_front(self, batch, jitter_grad, rays_only: bool = False) -> dict:
+    def _grad_front(self, batch, jitter_grad, rays_only: bool = False) -> GradFront:
         """the third render up to (not including) the first host read: supervision timestamps at grad.ts, poses and rays with
         their time derivatives, ray/AABB test, march count pass, scan (robust_e_nerf.py:340-357,383-409).  rays_only: without
         the last three (the "merged" placement marches these rays together with the l_diff render's)"""
@@ -1342,7 +1250,7 @@ class Trainer:
             o, d, od, dd = jvp.raygen_jvp(self.Kinv, batch["position"].contiguous(), pos, rot, dpos, drot)
         jit = None if jitter_grad is None else jitter_grad.to(torch.float32).contiguous()
         st = None if rays_only else self.r.sample_begin(o, d, jit, True, device_counts=self._dc_mode())
-        return dict(prep=prep, o=o, d=d, od=od, dd=dd, ddd=ddd, jit=jit, st=st)
+        return GradFront(prep, o, d, od, dd, ddd, jit, st)
 
     def begin_grad_sampling(self, batch, jitter_grad=None, merged: bool = False) -> bool:
         """Announce the third render of the step that is ABOUT to run -- call it before forward_backward(); the matching
@@ -1354,49 +1262,7 @@ class Trainer:
         count reads of the l_diff render leave on the main stream, and the host work of enqueuing them never delays the
         l_diff render (a step that starts on an empty queue -- trainable tau: its Adam group reads d loss / d tau back at the
         end of the step -- is host-bound right there).  Trainer.step does this when the l_grad term is on."""
-        if not self.r.field.flat.is_cuda or not (self.t.w_grad > 0):
-            return False
-        ready = None
-        if not merged:
-            ready = torch.cuda.Event()
-            ready.record()
-        self._grad_begun, self._grad_pending = None, (batch, jitter_grad, ready)
-        return True
-
-    def _begin_with_grad(self, o, d, jitter, dc):
-        """the l_diff render's sample_begin(), with the announced third render's front placed as its mode asks: "begun" -- this
-        render's count pass first, then the third render's front on the side stream; "merged" -- both renders' rays through
-        one ray / box test and one march count pass, in order on this stream"""
-        if self._grad_pending[2] is not None:                     # (an event: "begun")
-            begun = self.r.sample_begin(o, d, jitter, True, device_counts=dc)
-            self._begin_grad_now()
-            return begun
-        (batch, jitter_grad, _), self._grad_pending = self._grad_pending, None
-        fr = self._grad_front(batch, jitter_grad, rays_only=True)
-        if (jitter is None) != (fr["jit"] is None):
-            raise ValueError("merged sampling: jitter for both the l_diff renders and the third one, or for neither")
-        begun, fr["st"] = self.r.sample_begin_merged([(o, d, jitter), (fr["o"], fr["d"], fr["jit"])], True, device_counts=dc)
-        fr["n_host"], fr["key"], fr["merged"] = None, (id(batch), id(jitter_grad)), True
-        self._grad_begun = fr
-        return begun
-
-    def _begin_grad_now(self):
-        pend, self._grad_pending = self._grad_pending, None
-        if pend is None:
-            return
-        batch, jitter_grad, ready = pend
-        side = self.side_stream
-        side.wait_event(ready)
-        with torch.cuda.stream(side):
-            fr = self._grad_front(batch, jitter_grad)
-            if fr["st"].get("dc") is None:                  # (device-side counts: nothing to read back)
-                if self._n_host_grad is None:
-                    self._n_host_grad = torch.empty(1, dtype=fr["st"]["total"].dtype).pin_memory()
-                self._n_host_grad.copy_(fr["st"]["total"].reshape(1), non_blocking=True)
-                fr["ev"] = torch.cuda.Event()
-                fr["ev"].record()
-        fr["n_host"], fr["key"] = self._n_host_grad, (id(batch), id(jitter_grad))
-        self._grad_begun = fr
+        return self.fronts.begin_grad_sampling(self, batch, jitter_grad, merged)
 
     def grad_loss_forward_backward(self, batch, jitter_grad=None, final: bool = True, early: bool = False):
         """Log-intensity-GRADIENT loss term (robust_e_nerf.py:340-357,383-409; loss.py:43-57): a third
@@ -1415,32 +1281,9 @@ class Trainer:
         from . import jvp
         r, t, f = self.r, self.t, self.r.field
         B = batch["position"].shape[0]
-        ready, self._ready_ev = self._ready_ev, None
-        begun, self._grad_begun, self._grad_pending = self._grad_begun, None, None
-        if begun is not None and (not early or begun["key"] != (id(batch), id(jitter_grad))):
-            begun = None                                                  # (begin_grad_sampling was for another call)
-        if begun is not None and begun.get("merged"):
-            early = False                                                 # merged front: the rest follows in order on this stream
-        # no matching front: in order, unless the caller asks for the experimental placement (early="all": everything
-        # beside the l_diff forward / backward; wrong rays observed there, see grad_sampling_mode)
-        early = bool(early) and f.flat.is_cuda and (begun is not None or (early == "all" and ready is not None))
-        main = torch.cuda.current_stream() if f.flat.is_cuda else None
-        if early and begun is None:
-            self.side_stream.wait_event(ready)
-        with (torch.cuda.stream(self.side_stream) if early else contextlib.nullcontext()):
-            fr = begun if begun is not None else self._grad_front(batch, jitter_grad)
-            prep, o, d, od, dd, ddd, jit, st = (fr[k] for k in ("prep", "o", "d", "od", "dd", "ddd", "jit", "st"))
-            target = prep["target_grad"]                                                        # loss.py:39-42
-            if "ev" in fr:                                                # count pass already ran: its total is in the pinned buffer
-                fr["ev"].synchronize()
-                st["n0"] = int(fr["n_host"][0])
-            pk = r.sample(o, d, jit, True, begun=st, device_counts=dc)
-            if early:
-                done = torch.cuda.Event()
-                done.record()
-        if early:
-            main.wait_event(done)
-            _adopt((prep, o, d, od, dd, ddd, jit, pk), main)
+        fr, pk = self.fronts.sample_grad(self, batch, jitter_grad, early, dc)      # (the announced front, or one made now)
+        prep, o, d, od, dd, ddd, jit = fr.prep, fr.o, fr.d, fr.od, fr.dd, fr.ddd, fr.jit
+        target = prep["target_grad"]                                                            # loss.py:39-42
         bkgd = torch.nn.functional.softplus(self.small[: f.C]) if t.bkgd_is_param else None
         colors, colords, opac, ctx = jvp.render_forward(r, o, d, od, dd, jit, bkgd, training=True, pk=pk)
         ch = self._channel_index(batch, 1)

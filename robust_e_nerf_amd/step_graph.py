@@ -155,7 +155,8 @@ class StepGraphs:
         if dump:
             g.enable_debug_mode()
         host_state = (tr.step_count, tr._tau_adam_steps, tr._ep_stale)
-        r._capture, tr._grad_begun, tr._grad_pending = cap, None, None
+        r._capture = cap
+        tr.fronts.reset()                            # (a front of the eager steps is not part of this one, nor this one's of theirs)
         try:
             with torch.cuda.graph(g, pool=self.pool):
                 loss, aux = tr._step_passes(st_batch, j0, None, j2, optimizer=tr.world_size == 1)
@@ -164,7 +165,8 @@ class StepGraphs:
             tr.use_graph = False
             return None
         finally:
-            r._capture, tr._grad_begun, tr._grad_pending = None, None, None
+            r._capture = None
+            tr.fronts.reset()
             tr.step_count, tr._tau_adam_steps, tr._ep_stale = host_state       # (nothing ran)
         tr.graph_captures += 1
         if dump:

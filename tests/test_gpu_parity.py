@@ -1745,7 +1745,8 @@ def test_early_sampling_of_the_third_render_is_exact(amd, full_table_cache):
             assert tr.begin_grad_sampling(batch, j2)
         loss_d, aux = tr.forward_backward(batch, j0, j1)
         loss_g, aux_g = tr.grad_loss_forward_backward(batch, j2, early=bool(early))
-        assert tr._ready_ev is None and tr._grad_begun is None   # consumed (or dropped) by the call
+        sf = tr.fronts
+        assert sf.pending is None and sf.begun is None and sf.ready_ev is None   # consumed (or dropped) by the call
         f = tr.r.field
         out.append((float(loss_d), float(loss_g), aux_g["n"], f.grad_all.clone(), tr.small_grad.clone(), tr.ct_grad.clone(),
                     aux_g["dlog_dt"].clone()))
@@ -1762,7 +1763,8 @@ def test_early_sampling_of_the_third_render_is_exact(amd, full_table_cache):
     tr.begin_grad_sampling(batch, dev(jit[0]) * 0.5)
     tr.forward_backward(batch, dev(jit[1]), dev(jit[2]))
     loss_o, aux_o = tr.grad_loss_forward_backward(batch, dev(jit[0]), early=True)
-    assert aux_o["n"] == a[2] and tr._grad_begun is None
+    assert aux_o["n"] == a[2]
+    assert tr.fronts.pending is None and tr.fronts.begun is None and tr.fronts.ready_ev is None
     # Trainer.step takes the early path; two steps (the second one reads the ratio the first one's Adam moved) vs in-order
     for tau_trainable, mode in ((False, "begun"), (True, "begun")):       # (Trainer.grad_sampling_mode)
         res = []

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_gpu_parity as T
 from oracle import hashgrid
-from robust_e_nerf_amd import ops, engine
+from robust_e_nerf_amd import ops, engine, fronts
 g = T.load_golden("training_step_diff")
 table = hashgrid.init_table(hashgrid.make_spec(), int(g["table_seed"]), float(g["table_scale"]), "mix32")
 sampler = sys.argv[1] if len(sys.argv) > 1 else "uniform"
@@ -14,7 +14,7 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 B = 4096
 VAR = os.environ.get("DIAG_VAR", "")
 if VAR == "prio0":
-    engine.Trainer.side_stream = property(lambda self: self.__dict__.setdefault("_side0", torch.cuda.Stream()))
+    fronts.StepFronts.side_stream = property(lambda self: self.__dict__.setdefault("_side0", torch.cuda.Stream()))
 dev = T.dev
 def run(use, sync_each=False):
     tr, _ = T._trainer_from_golden(engine, g, table, sampler=sampler)

@@ -23,11 +23,11 @@ def run(use):
     torch.cuda.synchronize()
     res = []
     for i in range(3):
-        pf = tr._prefetched
+        pf = tr.fronts.prefetched                # (key, DiffFront, event, inputs)
         fr = None
         def flat(front):
-            st = front["begun"]
-            d_ = dict(o=front["o"], d=front["d"], jitter=front["jitter"], ts=front["prep"]["ts"], target=front["prep"]["target_diff"],
+            st = front.begun
+            d_ = dict(o=front.o, d=front.d, jitter=front.jitter, ts=front.prep["ts"], target=front.prep["target_diff"],
                       counts=st["counts"], offsets=st["offsets"], total=st["total"], t_min=st["args"][2], t_max=st["args"][3])
             if st["cache"] is not None:
                 d_["cache"] = st["cache"]
@@ -40,7 +40,7 @@ def run(use):
         else:
             # the same front, computed in order on the main stream (reference for the prefetched one)
             f0 = tr._front(*steps[i])
-            f0["begun"] = tr.r.sample_begin(f0["o"], f0["d"], f0["jitter"], True)
+            f0.begun = tr.r.sample_begin(f0.o, f0.d, f0.jitter, True)
             fr = {k: v.clone() for k, v in flat(f0).items()}
             live = None
         loss, aux = tr.forward_backward(*steps[i])

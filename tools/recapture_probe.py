@@ -42,7 +42,7 @@ if os.environ.get("STREAM"):                       # all of it on a non-default 
     _s = torch.cuda.Stream(priority=-1 if os.environ["STREAM"] == "high" else 0)
     torch.cuda.set_stream(_s)
 if os.environ.get("SIDE_PRIO"):                    # the trainer's side stream at normal priority
-    tr._side = torch.cuda.Stream()
+    tr.fronts._side = torch.cuda.Stream()
 run(6, "warm-up (host counts, capture)")
 if os.environ.get("PHASE") == "A":
     run(100, "graph 1")

@@ -907,6 +907,62 @@ int ren_mesh_components(const float *sigma, int32_t nx, int32_t ny, int32_t nz, 
 int ren_mesh_component_apply(const float *sigma, const int32_t *label, const uint8_t *drop, int64_t n, float value, float *out,
                              void *stream);
 
+/* ---- mesh simplify (csrc/ren_mesh_simplify.hip) -------------------------------------------------------- *
+ * Simplification of a triangle list by vertex clustering (Rossignac - Borrel): one vertex per occupied cell of a regular grid.
+ * Everything below is fixed by the input, so the output is the same bit for bit on every run and can be restated on the CPU.
+ * Input: verts (V, 3) float32; faces (F, 3) int32, ANY triangle list; a world box lo < hi (finite doubles on the HOST); a
+ * cluster grid g = (gx, gy, gz), each >= 1, gx gy gz <= REN_MESH_MAX_POINTS; V and F below 2^31.
+ * All real arithmetic is float64, every operation rounded on its own, with inv_a = g_a / (hi_a - lo_a) and
+ * cw_a = (hi_a - lo_a) / g_a formed once on the host.
+ * Cell of a vertex, per axis: r = (double(x_a) - lo_a) * inv_a, fl = floor(r); c_a = 0 if not fl >= 0 (NaN lands here), g_a - 1
+ * if fl >= g_a, else int(fl).  Cell id (c_x * gy + c_y) * gz + c_z.  A vertex outside the box is clamped into the border cells;
+ * nothing is refused for its position.
+ * Representative: frac = r - double(c_a), 0 if not frac >= 0, 1 if frac > 1; q = uint64(floor(frac * 1048576.0 + 0.5)), in
+ * [0, 2^20].  Per cell the three sums of q (uint64, below 2^51) and the member count (uint32) are accumulated with INTEGER
+ * atomic adds: order-independent.  Position of the cell's vertex, per axis:
+ *     float32(lo_a + (double(c_a) + double(sum_a) / double(count) / 1048576.0) * cw_a)
+ * Provisional ids: the occupied cells in ascending cell id; id = coff[cell], coff the exclusive prefix sum (int64,
+ * ren_exclusive_scan) of the occupied flags, `clusters` its total.
+ * Faces: every corner is replaced by its cell's provisional id.  A face is DEGENERATE, and dropped, when a corner index is
+ * outside [0, V) or two of its three ids are equal; the corner is range-checked before anything is read through it.  The KEY of
+ * another face is its id triple rotated so that the smallest id comes first -- a rotation keeps the orientation: (A, B, C) and
+ * (A, C, B) have different keys and both stay.  Among faces of equal key the one with the smallest input index survives, the
+ * others are DUPLICATES.  Kept faces stay in input order and keep their own corner order, not the rotated one.
+ * Orphans: a provisional vertex that no kept face references is removed; the others are renumbered in order (final id =
+ * uoff[provisional id], the exclusive prefix sum of the used flags) and the faces follow.
+ * Duplicates are found by ORDER, one method for every size: ren_mesh_simplify_faces writes the key as key_a = smallest id (int32)
+ * and key_b = second << 31 | third (int64), INT32_MAX / INT64_MAX for a degenerate face; the caller orders the faces by (key_a,
+ * key_b) with STABLE sorts (`order`: the input index at each sorted position), so that equal keys are adjacent in ascending
+ * input index and the first of a run is its survivor.
+ * ren_mesh_simplify_cells: cell[v] (int32), and sums (3 uint64 per cell) / count (uint32 per cell) += the members; the caller
+ *   zeroes sums and count.  One launch, one vertex per lane; V == 0 launches nothing.
+ * ren_mesh_simplify_flags: flag[c] (int32) = count[c] != 0.  One launch, one cell per lane.
+ * ren_mesh_simplify_faces: ids (F, 3) int32 provisional ids ((-1, -1, -1) for a degenerate face), key_a, key_b, and
+ *   *degenerate (int32, zeroed by the caller) += the number of degenerate faces.  One launch, one face per lane; F == 0 none.
+ * ren_mesh_simplify_heads: keep[f] (int32) = 1 for the survivors, else 0; used[id] (int32, `clusters` entries zeroed by the
+ *   caller) = 1 for every provisional id a survivor references.  One launch, one sorted position per lane; F == 0 none.
+ * ren_mesh_simplify_vertices: the representative of every used cluster at row uoff[id] of verts (V_out, 3) float32, V_out the
+ *   total of the used flags.  One launch, one cell per lane; V_out == 0 launches nothing.
+ * ren_mesh_simplify_compact_faces: faces (F_out, 3) int32, row foff[f] (the exclusive prefix sum of keep, F_out its total) =
+ *   uoff[ids[f]] per corner for the kept faces.  One launch, one face per lane; F_out == 0 launches nothing.
+ * Every index read from memory (cell, coff, order, ids, foff, uoff) is compared with the extent of what it indexes before use.
+ * Dense device memory: 28 B per cell for sums and count, 12 B more for the flag and its prefix sum; 30 GB + 13 GB at the cap.
+ * REN_ERR_BAD_ARG before any launch for a null or misaligned pointer (one that a zero count leaves unused may be null), a grid
+ * extent below 1, more than REN_MESH_MAX_POINTS cells, a count that is negative or 2^31 and beyond, clusters above the cells, V_out
+ * above clusters, F_out above F, a box that is not finite with lo < hi. */
+int ren_mesh_simplify_cells(const float *verts, int64_t V, const double *lo, const double *hi, int32_t gx, int32_t gy, int32_t gz,
+                            int32_t *cell, uint64_t *sums, uint32_t *count, void *stream);
+int ren_mesh_simplify_flags(const uint32_t *count, int64_t n_cells, int32_t *flag, void *stream);
+int ren_mesh_simplify_faces(const int32_t *faces, int64_t F, int64_t V, const int32_t *cell, const int64_t *coff, int64_t n_cells,
+                            int64_t clusters, int32_t *ids, int32_t *key_a, int64_t *key_b, int32_t *degenerate, void *stream);
+int ren_mesh_simplify_heads(const int64_t *order, const int32_t *key_a, const int64_t *key_b, const int32_t *ids, int64_t F,
+                            int64_t clusters, int32_t *keep, int32_t *used, void *stream);
+int ren_mesh_simplify_vertices(const uint64_t *sums, const uint32_t *count, const int64_t *coff, const int32_t *used,
+                               const int64_t *uoff, int32_t gx, int32_t gy, int32_t gz, const double *lo, const double *hi,
+                               int64_t clusters, int64_t V_out, float *verts, void *stream);
+int ren_mesh_simplify_compact_faces(const int32_t *ids, const int32_t *keep, const int64_t *foff, const int64_t *uoff, int64_t F,
+                                    int64_t clusters, int64_t F_out, int32_t *faces, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

@@ -165,6 +165,13 @@ SIGNATURES = {
                                c_int64, c_int64, P, P, P]),
     "ren_mesh_components": (c_int, [P, c_int32, c_int32, c_int32, c_float, c_int32, P, P, P, P]),
     "ren_mesh_component_apply": (c_int, [P, P, P, c_int64, c_float, P, P]),
+    "ren_mesh_simplify_cells": (c_int, [P, c_int64, POINTER(c_double), POINTER(c_double), c_int32, c_int32, c_int32, P, P, P, P]),
+    "ren_mesh_simplify_flags": (c_int, [P, c_int64, P, P]),
+    "ren_mesh_simplify_faces": (c_int, [P, c_int64, c_int64, P, P, c_int64, c_int64, P, P, P, P, P]),
+    "ren_mesh_simplify_heads": (c_int, [P, P, P, P, c_int64, c_int64, P, P, P]),
+    "ren_mesh_simplify_vertices": (c_int, [P, P, P, P, P, c_int32, c_int32, c_int32, POINTER(c_double), POINTER(c_double), c_int64,
+                                           c_int64, P, P]),
+    "ren_mesh_simplify_compact_faces": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P]),
 }
 
 _lib = None

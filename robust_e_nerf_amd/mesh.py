@@ -13,6 +13,10 @@ drop them.  The whole lattice lives in device memory at once.
 `clean` (export's min_points / largest / fill_cavities) rewrites the lattice before the extraction: floaters -- small connected
 components of the inside points -- are dropped and cavities -- outside components that reach no face of the lattice -- are
 filled, with the components labelled on the GPU (`components`: ops.mesh_components, include/ren_amd.h "mesh components").
+
+`simplify` (export's simplify=k) reduces the extracted mesh by vertex clustering: one vertex per occupied cell of a grid of k
+lattice spacings (`cluster_grid`), collapsed and repeated faces dropped (ops.mesh_simplify_*, include/ren_amd.h "mesh
+simplify").  The lattice resolution then sets the fidelity of the sampling and k the size of the file.
 """
 from __future__ import annotations
 
@@ -156,6 +160,62 @@ def clean(sigma: torch.Tensor, level: float, min_points: int = 1, largest: Optio
     return sigma, stats
 
 
+def cluster_grid(res: Res, k: float) -> Tuple[int, int, int]:
+    """the cluster grid of `simplify` for a lattice of `res` points per axis and clusters of k lattice spacings (k >= 1, not
+    necessarily whole): g_a = max(1, ceil((n_a - 1) / k)).  k = 1 gives one cell per cube of the lattice."""
+    try:
+        k = float(k)
+    except (TypeError, ValueError):
+        raise ValueError(f"mesh.cluster_grid: k is a number >= 1; got {k!r}") from None
+    if not math.isfinite(k) or k < 1:
+        raise ValueError(f"mesh.cluster_grid: k is a finite number >= 1; got {k!r}")
+    return tuple(max(1, math.ceil((n - 1) / k)) for n in _resolution(res))
+
+
+def simplify(verts: torch.Tensor, faces: torch.Tensor, lo: Sequence[float], hi: Sequence[float], grid: Sequence[int]):
+    """verts (V, 3) float32, faces (F, 3) int32 (any triangle list) -> (verts', faces', stats): vertex clustering over the
+    `grid` = (gx, gy, gz) cells of the world box [lo, hi] (include/ren_amd.h "mesh simplify").  Every occupied cell becomes
+    one vertex at the mean of its members (integer sums: bit-identical from run to run); faces with two corners in one cell
+    or a corner index outside [0, V) are dropped as degenerate, faces that repeat an earlier one's cells in the same
+    orientation as duplicates, vertices no kept face references as orphans.  Kept faces stay in input order.
+    stats: clusters (occupied cells), degenerate, duplicate, orphans.  Two host synchronisations (the number of clusters; the
+    other totals); two stable torch.sort calls order the faces by their key, everything else is the library's kernels.
+    ValueError before any launch for a wrong dtype, layout or device, a box that is not finite with lo < hi, a grid extent
+    below 1 or more than 2^30 cells."""
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError(f"mesh.simplify: faces must be a contiguous (F, 3) int32 device tensor; got {tuple(faces.shape)} "
+                         f"{faces.dtype} on {faces.device}")
+    if faces.shape[0] >= ops.MESH_MAX_VERTS:
+        raise ValueError(f"mesh.simplify: {faces.shape[0]} faces; the count must stay below 2^31")
+    cell, sums, count = ops.mesh_simplify_cells(verts, lo, hi, grid)              # checks verts, the box and the grid
+    n_verts, n_faces, dev = int(verts.shape[0]), int(faces.shape[0]), verts.device
+    empty = (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int32))
+    stats = dict(clusters=0, degenerate=n_faces, duplicate=0, orphans=0)
+    if n_verts == 0:                                                  # no cell is occupied: every face is out of range
+        return (*empty, stats)
+    coff, total = ops.exclusive_scan(ops.mesh_simplify_flags(count))
+    clusters = int(total)
+    stats.update(clusters=clusters, orphans=clusters)
+    if n_faces == 0:
+        return (*empty, stats)
+    ids, key_a, key_b, degenerate = ops.mesh_simplify_faces(faces, n_verts, cell, coff, clusters)
+    # lexicographic by (key_a, key_b): stable by the minor word, then stable by the major one
+    by_b = torch.sort(key_b, stable=True).indices
+    order = by_b[torch.sort(key_a[by_b], stable=True).indices]
+    keep, used = ops.mesh_simplify_heads(order, key_a, key_b, ids, clusters)
+    del order, by_b, key_a, key_b
+    foff, f_total = ops.exclusive_scan(keep)
+    uoff, u_total = ops.exclusive_scan(used)
+    n_degenerate, f_out, v_out = torch.cat([degenerate.to(torch.int64), f_total, u_total]).tolist()
+    stats.update(degenerate=n_degenerate, duplicate=n_faces - n_degenerate - f_out, orphans=clusters - v_out)
+    if f_out == 0:
+        return (*empty, stats)
+    new_verts = ops.mesh_simplify_vertices(sums, count, coff, used, uoff, lo, hi, grid, v_out)
+    return new_verts, ops.mesh_simplify_compact_faces(ids, keep, foff, uoff, f_out), stats
+
+
+_simplify = simplify                     # `export` has a parameter of the function's name
+
 def vertex_normals(r, verts: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
     """(V, 3) float32: -grad sigma / |grad sigma| at the vertices (r.density_gradient: arch ngp; arch mlp raises
     NotImplementedError); a zero gradient gives a zero normal"""
@@ -192,11 +252,16 @@ def write_ply(path: str, verts, faces, normals=None) -> None:
 
 
 def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None,
-           normals: bool = True, min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False) -> dict:
-    """sample, (clean,) extract, (normals,) write `path`; the box defaults to the renderer's cfg.aabb.
+           normals: bool = True, min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False,
+           simplify: Optional[float] = None) -> dict:
+    """sample, (clean,) extract, (simplify,) (normals,) write `path`; the box defaults to the renderer's cfg.aabb.
     -> dict(verts=V, faces=F, resolution=(nx, ny, nz), normals=bool); with min_points > 1, largest or fill_cavities the lattice
-    goes through `clean` first and the dict carries its stats as well"""
+    goes through `clean` first and the dict carries its stats as well.  With `simplify` = k >= 1 the extracted mesh goes
+    through `simplify` on the grid `cluster_grid(res, k)` -- clusters of k lattice spacings -- before the normals are taken
+    at the new positions; the dict then carries its stats (clusters, degenerate, duplicate, orphans), cluster_grid, and the
+    counts before the simplification as extracted_verts / extracted_faces."""
     _rule(min_points, largest)
+    grid = None if simplify is None else cluster_grid(res, simplify)
     aabb = [float(v) for v in r.cfg.aabb]
     lo = aabb[:3] if lo is None else lo
     hi = aabb[3:] if hi is None else hi
@@ -209,6 +274,11 @@ def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] =
         sigma, cleaned = clean(sigma, level, min_points, largest, fill_cavities)
     verts, faces = extract(sigma, level, lo, hi)
     del sigma
+    simplified = {}
+    if grid is not None:
+        extracted = dict(extracted_verts=int(verts.shape[0]), extracted_faces=int(faces.shape[0]))
+        verts, faces, simplified = _simplify(verts, faces, lo, hi, grid)
+        simplified = dict(simplified, cluster_grid=grid, **extracted)
     nrm = vertex_normals(r, verts) if normals else None
     write_ply(path, verts, faces, nrm)
-    return dict(verts=int(verts.shape[0]), faces=int(faces.shape[0]), resolution=res, normals=bool(normals), **cleaned)
+    return dict(verts=int(verts.shape[0]), faces=int(faces.shape[0]), resolution=res, normals=bool(normals), **cleaned, **simplified)

@@ -888,6 +888,122 @@ def mesh_component_apply(sigma: torch.Tensor, label: torch.Tensor, drop: torch.T
     return out
 
 
+# ------------------------------------------------------------------------------- mesh simplify (vertex clustering)
+def _simplify_grid(lo: Sequence[float], hi: Sequence[float], grid: Sequence[int], what: str):
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"{what}: the box needs finite lo < hi on every axis; got {lo}, {hi}")
+    g = tuple(grid)
+    if len(g) != 3 or any(int(v) != v or v < 1 for v in g):
+        raise ValueError(f"{what}: the cluster grid is three integers >= 1; got {grid!r}")
+    g = tuple(int(v) for v in g)
+    if g[0] * g[1] * g[2] > MESH_MAX_POINTS:
+        raise ValueError(f"{what}: a cluster grid of {g} has more than 2^30 cells")
+    d3 = ctypes.c_double * 3
+    return d3(*lo), d3(*hi), g
+
+
+def _rows(t: torch.Tensor, cols, what: str):
+    want = "(n,)" if cols is None else f"(n, {cols})"
+    if t.dim() != (1 if cols is None else 2) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{what} must be {want}; got {tuple(t.shape)}")
+    if t.shape[0] >= MESH_MAX_VERTS:
+        raise ValueError(f"{what}: {t.shape[0]} rows; the count must stay below 2^31")
+    return int(t.shape[0])
+
+
+def mesh_simplify_cells(verts: torch.Tensor, lo: Sequence[float], hi: Sequence[float], grid: Sequence[int]):
+    """verts (V, 3) float32 -> cell (V,) int32: the cluster cell of every vertex, sums (cells, 3) int64 (the bits of uint64)
+    and count (cells,) int32 (the bits of uint32): per cell the integer sums of the members' quantised offsets and their
+    number (include/ren_amd.h "mesh simplify").  V == 0 launches nothing."""
+    plo, phi, g = _simplify_grid(lo, hi, grid, "mesh_simplify_cells")
+    pv = _ptr(verts, torch.float32)
+    n = _rows(verts, 3, "mesh_simplify_cells: verts")
+    dev, cells = verts.device, g[0] * g[1] * g[2]
+    cell = torch.empty(n, device=dev, dtype=torch.int32)
+    sums = torch.zeros(cells, 3, device=dev, dtype=torch.int64)
+    count = torch.zeros(cells, device=dev, dtype=torch.int32)
+    check(_lib.load().ren_mesh_simplify_cells(pv, n, plo, phi, *g, _ptr(cell), _ptr(sums), _ptr(count), _stream()),
+          "ren_mesh_simplify_cells")
+    return cell, sums, count
+
+
+def mesh_simplify_flags(count: torch.Tensor) -> torch.Tensor:
+    """count (cells,) int32 -> flag (cells,) int32: 1 where the cell has a member, for exclusive_scan"""
+    pc = _ptr(count, torch.int32)
+    n = _rows(count, None, "mesh_simplify_flags: count")
+    flag = torch.empty(n, device=count.device, dtype=torch.int32)
+    check(_lib.load().ren_mesh_simplify_flags(pc, n, _ptr(flag), _stream()), "ren_mesh_simplify_flags")
+    return flag
+
+
+def mesh_simplify_faces(faces: torch.Tensor, n_verts: int, cell: torch.Tensor, coff: torch.Tensor, clusters: int):
+    """faces (F, 3) int32 over n_verts vertices, cell (n_verts,) int32, coff (cells,) int64: the exclusive prefix sum of the
+    occupied flags, `clusters` its total -> ids (F, 3) int32: the provisional id of every corner, (-1, -1, -1) for a
+    degenerate face; key_a (F,) int32 and key_b (F,) int64: the rotation-invariant key, at their maximum for a degenerate
+    face; degenerate (1,) int32: their number.  F == 0 launches nothing."""
+    ptrs = (_ptr(faces, torch.int32), _ptr(cell, torch.int32), _ptr(coff, torch.int64))
+    n = _rows(faces, 3, "mesh_simplify_faces: faces")
+    n_verts, clusters, cells = int(n_verts), int(clusters), _rows(coff, None, "mesh_simplify_faces: coff")
+    if cell.shape != (n_verts,) or not 0 <= clusters <= cells:
+        raise ValueError(f"mesh_simplify_faces: cell must be ({n_verts},) and clusters in [0, {cells}]")
+    dev = faces.device
+    ids = torch.empty(n, 3, device=dev, dtype=torch.int32)
+    key_a = torch.empty(n, device=dev, dtype=torch.int32)
+    key_b = torch.empty(n, device=dev, dtype=torch.int64)
+    degenerate = torch.zeros(1, device=dev, dtype=torch.int32)
+    check(_lib.load().ren_mesh_simplify_faces(ptrs[0], n, n_verts, ptrs[1], ptrs[2], cells, clusters, _ptr(ids), _ptr(key_a),
+                                              _ptr(key_b), _ptr(degenerate), _stream()), "ren_mesh_simplify_faces")
+    return ids, key_a, key_b, degenerate
+
+
+def mesh_simplify_heads(order: torch.Tensor, key_a: torch.Tensor, key_b: torch.Tensor, ids: torch.Tensor, clusters: int):
+    """order (F,) int64: the face at every position of the stable lexicographic order by (key_a, key_b) -> keep (F,) int32: 1
+    for the first face of every run of equal keys that is not degenerate; used (clusters,) int32: 1 for the provisional ids
+    the kept faces reference.  F == 0 launches nothing."""
+    ptrs = (_ptr(order, torch.int64), _ptr(key_a, torch.int32), _ptr(key_b, torch.int64), _ptr(ids, torch.int32))
+    n = _rows(ids, 3, "mesh_simplify_heads: ids")
+    clusters = int(clusters)
+    if order.shape != (n,) or key_a.shape != (n,) or key_b.shape != (n,) or not 0 <= clusters <= MESH_MAX_POINTS:
+        raise ValueError(f"mesh_simplify_heads: order, key_a and key_b must be ({n},) and clusters in [0, 2^30]")
+    keep = torch.zeros(n, device=ids.device, dtype=torch.int32)
+    used = torch.zeros(clusters, device=ids.device, dtype=torch.int32)
+    check(_lib.load().ren_mesh_simplify_heads(*ptrs, n, clusters, _ptr(keep), _ptr(used), _stream()), "ren_mesh_simplify_heads")
+    return keep, used
+
+
+def mesh_simplify_vertices(sums: torch.Tensor, count: torch.Tensor, coff: torch.Tensor, used: torch.Tensor, uoff: torch.Tensor,
+                           lo: Sequence[float], hi: Sequence[float], grid: Sequence[int], n_out: int) -> torch.Tensor:
+    """-> verts (n_out, 3) float32: the representative of every used cluster at row uoff[provisional id]; uoff (clusters,)
+    int64 the exclusive prefix sum of `used`, n_out its total.  n_out == 0 launches nothing."""
+    plo, phi, g = _simplify_grid(lo, hi, grid, "mesh_simplify_vertices")
+    ptrs = (_ptr(sums, torch.int64), _ptr(count, torch.int32), _ptr(coff, torch.int64), _ptr(used, torch.int32),
+            _ptr(uoff, torch.int64))
+    cells, clusters, n_out = g[0] * g[1] * g[2], _rows(used, None, "mesh_simplify_vertices: used"), int(n_out)
+    if sums.shape != (cells, 3) or count.shape != (cells,) or coff.shape != (cells,) or uoff.shape != (clusters,):
+        raise ValueError(f"mesh_simplify_vertices: sums ({cells}, 3), count / coff ({cells},), uoff ({clusters},) expected")
+    if not 0 <= n_out <= clusters <= cells:
+        raise ValueError(f"mesh_simplify_vertices: 0 <= n_out <= clusters <= cells; got {n_out}, {clusters}, {cells}")
+    verts = torch.empty(n_out, 3, device=sums.device, dtype=torch.float32)
+    check(_lib.load().ren_mesh_simplify_vertices(*ptrs, *g, plo, phi, clusters, n_out, _ptr(verts), _stream()),
+          "ren_mesh_simplify_vertices")
+    return verts
+
+
+def mesh_simplify_compact_faces(ids: torch.Tensor, keep: torch.Tensor, foff: torch.Tensor, uoff: torch.Tensor,
+                                n_out: int) -> torch.Tensor:
+    """-> faces (n_out, 3) int32: the kept faces in input order with their final vertex ids uoff[provisional id]; foff (F,)
+    int64 the exclusive prefix sum of keep, n_out its total.  n_out == 0 launches nothing."""
+    ptrs = (_ptr(ids, torch.int32), _ptr(keep, torch.int32), _ptr(foff, torch.int64), _ptr(uoff, torch.int64))
+    n, clusters, n_out = _rows(ids, 3, "mesh_simplify_compact_faces: ids"), _rows(uoff, None, "mesh_simplify_compact_faces: uoff"), int(n_out)
+    if keep.shape != (n,) or foff.shape != (n,) or not 0 <= n_out <= n or clusters > MESH_MAX_POINTS:
+        raise ValueError(f"mesh_simplify_compact_faces: keep / foff must be ({n},), n_out in [0, {n}], at most 2^30 clusters")
+    faces = torch.empty(n_out, 3, device=ids.device, dtype=torch.int32)
+    check(_lib.load().ren_mesh_simplify_compact_faces(*ptrs, n, clusters, n_out, _ptr(faces), _stream()),
+          "ren_mesh_simplify_compact_faces")
+    return faces
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 
@@ -1086,7 +1202,9 @@ _TIMED = ("ray_aabb_intersect", "ray_march_count", "ray_march_write", "exclusive
           "compact_samples", "compact_features", "hashgrid_fwd", "hashgrid_bwd", "hashgrid_bwd_input", "hashgrid_bwd_binned", "hashgrid_bwd_binned_begin",
           "hashgrid_bwd_binned_scatter", "hashgrid_bwd_binned_finish", "mlp_fwd", "mlp_bwd", "mlp_fwd_save",
           "mlp_bwd_saved", "mlp_fwd_x", "mlp_bwd_x", "composite_fwd",
-          "composite_bwd", "column_sum", "event_loss_fwd", "event_loss_bwd", "adam_step", "trajectory", "raygen")
+          "composite_bwd", "column_sum", "event_loss_fwd", "event_loss_bwd", "adam_step", "trajectory", "raygen",
+          "mesh_simplify_cells", "mesh_simplify_flags", "mesh_simplify_faces", "mesh_simplify_heads", "mesh_simplify_vertices",
+          "mesh_simplify_compact_faces")
 
 
 def profile_start():

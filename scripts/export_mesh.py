@@ -2,16 +2,19 @@
 
     python scripts/export_mesh.py --config <YAML> --ckpt runs/train/last.ckpt --out mesh.ply \
         [--resolution N | --resolution NX NY NZ] [--level L] [--aabb x0 y0 z0 x1 y1 z1] [--no-normals]
-        [--min-component N] [--largest K] [--fill-cavities]
+        [--min-component N] [--largest K] [--fill-cavities] [--simplify K]
 
 The field is loaded as scripts/render.py loads it.  The density is sampled on a regular lattice of --resolution points per
 axis over --aabb (default: the model's box), the surface sigma = --level is extracted on the GPU (robust_e_nerf_amd/mesh.py)
 and every vertex gets the direction of -grad sigma as its normal, the convention of `render.py --normals`.  Arch mlp has no
 density gradient: its mesh is written without normals.  --min-component / --largest drop floaters (connected pieces of the
-solid, counted in lattice points) and --fill-cavities closes the voids inside objects before the extraction (mesh.clean).  `model.nerf.aabb: auto` spans the camera positions, so it needs
+solid, counted in lattice points) and --fill-cavities closes the voids inside objects before the extraction (mesh.clean).
+--simplify K merges the vertices within each cell of K lattice spacings into one (vertex clustering, mesh.simplify): sample
+finely for the geometry, simplify for a file a viewer can hold.  `model.nerf.aabb: auto` spans the camera positions, so it needs
 --dataset-dir, --synthetic or an explicit --aabb.
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -40,6 +43,8 @@ def parse_args(argv=None):
     ap.add_argument("--largest", type=int, metavar="K", help="keep only the K largest connected pieces of the solid")
     ap.add_argument("--fill-cavities", action="store_true",
                     help="fill the voids that reach no face of the lattice: no inner surface of a hollow object")
+    ap.add_argument("--simplify", type=float, metavar="K",
+                    help="simplify the mesh by vertex clustering: one vertex per cell of K lattice spacings, K >= 1 (default: off)")
     ap.add_argument("--dataset-dir", help="camera poses for `aabb: auto` (default: the YAML's data.dataset_directory)")
     ap.add_argument("--synthetic", action="store_true", help="`aabb: auto` from the synthetic benchmark orbit")
     args = ap.parse_args(argv)
@@ -47,6 +52,8 @@ def parse_args(argv=None):
         ap.error("--resolution takes one value or three")
     if args.min_component < 1 or (args.largest is not None and args.largest < 1):
         ap.error("--min-component and --largest take integers >= 1")
+    if args.simplify is not None and not (math.isfinite(args.simplify) and args.simplify >= 1):
+        ap.error("--simplify takes a finite number >= 1")
     args.resolution = tuple(args.resolution * 3 if len(args.resolution) == 1 else args.resolution)
     return args
 
@@ -78,7 +85,7 @@ def main(argv=None):
     lo, hi = (args.aabb[:3], args.aabb[3:]) if args.aabb else (None, None)
     t0 = time.perf_counter()
     stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals, min_points=args.min_component,
-                        largest=args.largest, fill_cavities=args.fill_cavities)
+                        largest=args.largest, fill_cavities=args.fill_cavities, simplify=args.simplify)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{stats['verts']} vertices, {stats['faces']} faces ({'with' if normals else 'no'} normals) at resolution "
@@ -86,6 +93,10 @@ def main(argv=None):
     if "components" in stats:
         print(f"{stats['components']} connected pieces, {stats['kept']} kept ({stats['dropped_points']} lattice points dropped); "
               f"{stats['cavities']} cavities filled ({stats['filled_points']} lattice points)", flush=True)
+    if "clusters" in stats:
+        print(f"simplified from {stats['extracted_verts']} vertices, {stats['extracted_faces']} faces on a cluster grid of "
+              f"{' x '.join(str(v) for v in stats['cluster_grid'])}: {stats['clusters']} clusters, {stats['degenerate']} collapsed and "
+              f"{stats['duplicate']} repeated faces dropped, {stats['orphans']} unreferenced vertices removed", flush=True)
 
 
 if __name__ == "__main__":

@@ -7,6 +7,8 @@ This is the "one level up" seam of SURVEY.md 8b: ``Renderer.forward`` replaces
 (robust_e_nerf/models/robust_e_nerf.py:301-517, 782-813) for the log-intensity-difference loss.
 Gradients are written straight into one flat buffer ([hash table | MLPs]) so the data-parallel
 all-reduce is a single RCCL call and Adam a single fused pass.
+Three concerns of the step live in objects of their own: the captured step (step_graph.StepGraphs), the side-stream fronts
+(fronts.StepFronts) and the device-side sample counts (sample_counts.SampleCounts, Renderer.counts).
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import torch
 
 from . import ops
 from .fronts import DiffFront, GradFront, StepFronts
+from .sample_counts import CountLog, SampleCounts, device_words
 from .step_graph import StepGraphs
 
 
@@ -220,52 +223,6 @@ def pack_batch(batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class CountLog:
-    """The two sample counts of one render sampled with device-side counts -- marched, kept -- and whether they fitted the
-    capacities the arrays were given: copied to pinned memory behind the sampling kernels.  wait() blocks the host until
-    THOSE kernels are done (an event), not until the queue is empty.
-    polled=True (a render inside a captured step, step_graph.StepGraphs): the copy is a node of the graph and no event can be
-    waited for; the host arms the pinned words with -1 before every replay (arm()) and wait() spins until the copy has
-    landed -- pinned host memory is coherent, and each of the four words is one aligned 8-byte store."""
-
-    def __init__(self, n_rays: int, caps, stats: torch.Tensor, pinned: torch.Tensor, polled: bool = False):
-        self.n_rays, self.caps, self.stats = n_rays, caps, stats
-        pinned.copy_(stats, non_blocking=True)
-        self._pinned = pinned
-        self.ev = None
-        if not polled:
-            self.ev = torch.cuda.Event()
-            self.ev.record()
-        self.values = None                       # (marched, overflowed, kept, overflowed)
-
-    def arm(self):
-        self._pinned.fill_(-1)
-        self.values = None
-
-    def wait(self):
-        if self.values is None:
-            if self.ev is not None:
-                self.ev.synchronize()
-                self.values = tuple(int(v) for v in self._pinned.tolist())
-            else:
-                import time
-                t0 = time.monotonic()
-                while True:
-                    v = self._pinned.tolist()
-                    if min(v) >= 0:
-                        break
-                    if time.monotonic() - t0 > 120.0:         # (a replay that died: fail loudly instead of spinning for ever)
-                        torch.cuda.synchronize()
-                        raise RuntimeError("captured step: the sample counts of a replay never arrived")
-                self.values = tuple(int(x) for x in v)
-        return self.values
-
-    @property
-    def overflowed(self) -> bool:
-        v = self.wait()
-        return bool(v[1] or v[3])
-
-
 _PINNED = threading.local()             # per host thread: two renderers may read counts from two threads at once
 
 
@@ -312,11 +269,8 @@ class Renderer:
         self._bwd_stream = None
         self._reuse_prepass_feat = True             # the differentiable pass reuses the pre-pass hash features
         self._march_div_ok = None                   # ops.march_div_check(cfg.aabb), at the first occupancy-sampled render
-        # device-side sample counts (RenderCfg.device_counts): samples per ray (marched, kept) the capacities are derived from,
-        # learnt from the renders themselves -- the first one reads its counts on the host -- and a ring of pinned buffers
-        self._spr = None
-        self._count_ring, self._count_ring_at = None, 0
-        self._capture = None                        # step_graph.Capture while a step is being captured
+        self.counts = SampleCounts()                # device-side sample counts (RenderCfg.device_counts): capacities, logs, repeats
+        self._capture = None                       # step_graph.Capture while a step is being captured
         self.dp_early_enabled = True                # the Trainer clears it when a loss pass may have to be repeated (device-side counts)
         self.bwd_side_cus = 0                       # CUs the persistent MLP backward kernels leave free (Trainer: a side stream is at work)
         self._act_code = ops.activation_code(cfg.base_hidden_activation, cfg.density_activation, cfg.head_hidden_activation,
@@ -393,19 +347,18 @@ class Renderer:
     def _scan_counts(self, st: dict, device_counts) -> dict:
         counts, mode, n_rays = st["counts"], st["mode"], st["counts"].shape[0]
         dcst = None
-        caps = self._capacities(n_rays) if (device_counts is True and mode == 0 and self.device_counts_ok()) else None
+        caps = self.counts.capacities(n_rays) if (device_counts is True and mode == 0 and self.device_counts_ok()) else None
         if caps is not None:
             # device-side counts: scan and first guard in one launch (sample() continues from here without a host read)
-            stats = torch.empty(4, device=counts.device, dtype=torch.int64)
-            nd = torch.empty(2, device=counts.device, dtype=torch.int64)
+            stats, nd = device_words(counts.device)
             offsets, total = ops.scan_guard(counts, caps[0], nd[0:1], stats[0:2])
             dcst = dict(caps=caps, stats=stats, nd=nd)
         else:
             offsets, total = ops.exclusive_scan(counts)
         return dict(st, offsets=offsets, total=total, dc=dcst)
 
-    # ---- device-side sample counts -----------------------------------------------------------------------------------
-    CAP_MARGIN, CAP_SLACK, CAP_MAX = 1.25, 4096, 1 << 23      # (from 2^23 samples on the chunked two-stream paths take over)
+    # ---- device-side sample counts (sample_counts.SampleCounts) -----------------------------------------------------
+    _spr = property(lambda self: self.counts.spr, lambda self, v: setattr(self.counts, "spr", v))   # (bench.py and the tests)
 
     def device_counts_ok(self) -> bool:
         """the kernels that take the count from the device: occupancy sampler, NGP field on the bf16-matrix-core MLP
@@ -414,43 +367,15 @@ class Renderer:
         return (c.device_counts is not False and c.sampler == "occgrid" and type(self) is Renderer and c.mlp_kernels == "x" and
                 c.binned_scatter and self.field.flat.is_cuda)
 
-    def _capacities(self, n_rays: int):
-        if self._spr is None:
-            return None
-        def bucket(x):                                   # 8 sizes per octave: the allocator sees repeating sizes while
-            q = max(1024, 1 << max(0, x.bit_length() - 4))      # the ray count drifts (update_train_batch_size)
-            return (x + q - 1) // q * q
-        caps = tuple(bucket(int(n_rays * s * self.CAP_MARGIN) + self.CAP_SLACK) for s in self._spr)
-        return None if max(caps) >= self.CAP_MAX else caps
-
-    def _learn_counts(self, n_rays: int, marched: int, kept: int):
-        """capacities follow the counts: up at once, down slowly (the occupancy grid prunes over the first epochs)"""
-        m = (marched / max(n_rays, 1), kept / max(n_rays, 1))
-        self._spr = m if self._spr is None else tuple(max(a, 0.75 * b + 0.25 * a) for a, b in zip(m, self._spr))
-
-    def _count_log(self, n_rays: int, caps, stats: torch.Tensor) -> CountLog:
-        if self._capture is not None:                            # inside a capture: the graph owns its pinned words
-            return CountLog(n_rays, caps, stats, self._capture.pinned.pop(), polled=True)   # (pinned before the capture began)
-        if self._count_ring is None:
-            self._count_ring = [torch.empty(4, dtype=torch.int64).pin_memory() for _ in range(16)]
-            self._count_logs = [None] * 16
-        k = self._count_ring_at = (self._count_ring_at + 1) % 16
-        if self._count_logs[k] is not None:
-            self._count_logs[k].wait()                       # (its pinned buffer is about to be reused)
-        log = self._count_logs[k] = CountLog(n_rays, caps, stats, self._count_ring[k])
-        return log
-
     def _sample_device_counts(self, o, d, st, caps, keep_feat: bool) -> Packed:
         """sample() without a host read: both counts stay on the device, every array has a capacity, two guards clear the
         render (and report it) should a count not fit"""
         c = self.cfg
         args, cache, counts, offsets = st["args"], st["cache"], st["counts"], st["offsets"]
-        dev = o.device
         if st.get("dc") is not None:                         # sample_begin ran the first guard with its scan
             caps, stats, nd = st["dc"]["caps"], st["dc"]["stats"], st["dc"]["nd"]
         else:
-            stats = torch.empty(4, device=dev, dtype=torch.int64)
-            nd = torch.empty(2, device=dev, dtype=torch.int64)
+            stats, nd = device_words(o.device)
             ops.count_guard(counts, st["total"], caps[0], nd[0:1], stats[0:2])
         cap0, cap1 = caps
         n0_dev, n1_dev = nd[0:1], nd[1:2]
@@ -464,7 +389,7 @@ class Renderer:
         new_offsets, total2 = ops.scan_guard(kept, cap1, n1_dev, stats[2:4], counts_also=counts)
         ri2, ts2, te2 = ops.compact_samples(offsets, counts, new_offsets, keep, ts, te, cap1)
         feat1 = ops.compact_features(offsets, counts, new_offsets, keep, feat0, cap1, n_dev=n1_dev) if feat0 is not None else None
-        log = self._count_log(o.shape[0], caps, stats)
+        log = self.counts.log(o.shape[0], caps, stats, self._capture)
         return Packed(ri2, ts2, te2, new_offsets, kept, cap1, cap0, feat1, n_dev=n1_dev, log=log)
 
     def sample(self, o, d, jitter: Optional[torch.Tensor], training: bool, keep_feat: bool = False,
@@ -479,7 +404,7 @@ class Renderer:
             st = self.sample_begin(o, d, jitter, training)
         args, cache, counts, offsets, mode = st["args"], st["cache"], st["counts"], st["offsets"], st["mode"]
         if dc_now:
-            caps = st["dc"]["caps"] if st.get("dc") is not None else self._capacities(o.shape[0])
+            caps = st["dc"]["caps"] if st.get("dc") is not None else self.counts.capacities(o.shape[0])
             if caps is not None:
                 return self._sample_device_counts(o, d, st, caps, keep_feat)
         # host sync, as in the reference (external/utils.py:106-119); `begun["n0"]`: already read back (Trainer.prefetch)
@@ -487,7 +412,7 @@ class Renderer:
         ri, ts, te = ops.ray_march_write(*args, offsets, n0, counts=counts, cache=cache)
         if mode == 1 or n0 == 0:
             if learn:
-                self._learn_counts(o.shape[0], n0, n0)
+                self.counts.learn(o.shape[0], n0, n0)
             return Packed(ri, ts, te, offsets, counts, n0, n0)
         # sigma_fn pre-pass (external/utils.py:68-81) + render_visibility
         keep_feat = keep_feat and self._reuse_prepass_feat and c.mlp_kernels == "x"
@@ -503,7 +428,7 @@ class Renderer:
         if feat0 is not None and n1 > 0:                     # the pre-pass already encoded every survivor
             feat1 = feat0 if n1 == n0 else ops.compact_features(offsets, counts, new_offsets, keep, feat0, n1)
         if learn:
-            self._learn_counts(o.shape[0], n0, n1)
+            self.counts.learn(o.shape[0], n0, n1)
         return Packed(ri2, ts2, te2, new_offsets, kept, n1, n0, feat1)
 
     # ---- field evaluation over a packed sample stream (overridden by vanilla.VanillaRenderer) ----------
@@ -953,13 +878,12 @@ class Trainer:
             self.sync = parallel.GradSync(process_group, world_size, compress=renderer.cfg.dp_compress)
             renderer.grad_sync = self.sync
         self._mean_s_dev = None                                  # samples / ray of this step, summed over ranks (device)
-        # device-side sample counts (RenderCfg.device_counts): the renders of the step in flight whose counts the host has
-        # not looked at yet, and how to repeat them should one not have fitted its arrays
+        # device-side sample counts (RenderCfg.device_counts): whether this trainer's renders use them; the rest is the
+        # renderer's sample_counts.SampleCounts (self.r.counts)
         self._device_counts: Optional[bool] = None               # the `device_counts` property: None = auto (device_counts_ok)
         if os.environ.get("REN_DEVICE_COUNTS", "") in ("0", "off"):  # A/B switch for scripts that build the trainer themselves
             self._device_counts = False
         self._update_dp_early()
-        self._dc_sync, self.device_count_overflows = False, 0
         self.keep_ctx = False                                    # tests: aux["ctx"] = the render's context (rays, samples, features)
         # optimiser state on the device (ABI 25, ops.HY_*): Adam step numbers and bias corrections, and the sticky skip word a
         # captured step raises when one of its device-side counts did not fit (step_graph.StepGraphs)
@@ -1024,51 +948,6 @@ class Trainer:
         """data parallelism: the early all-reduce inside the last backward pass only while no pass can be repeated"""
         if self.world_size > 1:
             self.r.dp_early_enabled = not self.device_counts_ok()
-
-    def _dc_mode(self):
-        """what this step's renders pass to Renderer.sample: True (counts stay on the device), "learn" (host counts, but the
-        capacities learn from them) or False"""
-        if not self.device_counts_ok():
-            return False
-        return "learn" if self._dc_sync else True
-
-    def _dc_pass(self, fn, args):
-        """Run one loss pass (`fn(*args, dc)` -> loss, aux, CountLog | None) with its sample counts on the device, then look
-        at them (_settle; its field evaluation and backward are still in the queue).  A count that did not fit its arrays left
-        the render empty: the scalar parameters' gradient block is put back and the pass runs again with host-side counts."""
-        dc, cap = self._dc_mode(), self.r._capture
-        snap = self._gs.clone() if dc is True and cap is None else None
-        loss, aux, log = fn(*args, dc)
-        if cap is not None:                                  # StepGraphs looks at the counts after every replay
-            if log is None:
-                raise RuntimeError("a captured step needs every render on device-side counts")
-            cap.passes.append((log, aux))
-        elif log is not None and self._settle([(log, aux)]):
-            self._gs.copy_(snap)         # (not _clear_grads: this pass added nothing to the table / MLP gradients, earlier ones did)
-            loss, aux, _ = self._repeat_with_host_counts(lambda: fn(*args, self._dc_mode()))
-        return loss, aux
-
-    def _settle(self, passes) -> bool:
-        """wait for the counts of loss passes [(CountLog, aux), ...] -> whether one did not fit; else the capacities and auxes get them"""
-        vals = [log.wait() for log, _ in passes]
-        if any(v[1] or v[3] for v in vals):
-            return True
-        for (log, aux), v in zip(passes, vals):
-            self.r._learn_counts(log.n_rays, v[0], v[2])
-            aux["n"] = v[2]
-            if "n_marched" in aux:
-                aux["n_marched"] = v[0]
-        return False
-
-    def _repeat_with_host_counts(self, fn):
-        """fn() again with host-side counts (the capacities learn from them), after a device-side count did not fit"""
-        self.device_count_overflows += 1
-        self._dc_sync = True
-        self.fronts.reset()
-        try:
-            return fn()
-        finally:
-            self._dc_sync = False
 
     def _clear_grads(self):
         self.r.field.grad_all.zero_()
@@ -1156,7 +1035,7 @@ class Trainer:
         backward pass (default: yes unless the log-intensity-gradient term follows)."""
         if final is None:
             final = not (self.t.w_grad > 0)
-        return self._dc_pass(self._forward_backward, (batch, jitter_start, jitter_end, final))
+        return self.r.counts.run_pass(self, self._forward_backward, (batch, jitter_start, jitter_end, final))
 
     def _forward_backward(self, batch, jitter_start, jitter_end, final, dc):
         r, t, f = self.r, self.t, self.r.field
@@ -1203,7 +1082,7 @@ class Trainer:
         d_bk = r.backward(ctx, g_colors, final=final, per_ray_bkgd=True)
         if d_bk is not None:
             ops.bkgd_param_grad(d_bk, self.small, self.small_grad)       # += sigmoid(raw) * column sums (d softplus)
-        pk = ctx["pk"]                                       # (pk.log: n / n_marched are capacities here, _dc_pass puts the counts in)
+        pk = ctx["pk"]                                       # (pk.log: n / n_marched are capacities here, SampleCounts.run_pass puts the counts in)
         aux = dict(intensity_start=i_s, intensity_end=i_e, n=pk.n, n_marched=pk.n_marched, opacity=opac, rays=2 * B)
         if self.keep_ctx:                                    # tests: the renders' own rays and samples
             aux["ctx"] = ctx
@@ -1249,7 +1128,7 @@ class Trainer:
             pos, rot, dpos, drot = jvp.trajectory_jvp(ts_g, self.tab_ts, self.tab_pos, self.tab_quat)
             o, d, od, dd = jvp.raygen_jvp(self.Kinv, batch["position"].contiguous(), pos, rot, dpos, drot)
         jit = None if jitter_grad is None else jitter_grad.to(torch.float32).contiguous()
-        st = None if rays_only else self.r.sample_begin(o, d, jit, True, device_counts=self._dc_mode())
+        st = None if rays_only else self.r.sample_begin(o, d, jit, True, device_counts=self.r.counts.mode(self.device_counts_ok()))
         return GradFront(prep, o, d, od, dd, ddd, jit, st)
 
     def begin_grad_sampling(self, batch, jitter_grad=None, merged: bool = False) -> bool:
@@ -1275,7 +1154,7 @@ class Trainer:
         the host reads then wait for a few small kernels instead of draining the queue twice.  Without a matching front the
         call runs in order.  Same arithmetic, same results.  (early="all": the experimental placement of
         grad_sampling_mode's docstring.)"""
-        return self._dc_pass(self._grad_loss_forward_backward, (batch, jitter_grad, final, early))
+        return self.r.counts.run_pass(self, self._grad_loss_forward_backward, (batch, jitter_grad, final, early))
 
     def _grad_loss_forward_backward(self, batch, jitter_grad, final, early, dc):
         from . import jvp
@@ -1491,3 +1370,4 @@ class Trainer:
 
     _graphs = property(lambda self: self.step_graphs.cache)          # (bench.py and the tests read these two)
     _graph_bad = property(lambda self: self.step_graphs.bad)
+    device_count_overflows = property(lambda self: self.r.counts.overflows)      # (and passes repeated with host counts)

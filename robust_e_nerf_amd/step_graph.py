@@ -9,6 +9,7 @@ from dataclasses import dataclass, field
 import torch
 
 from . import ops
+from .sample_counts import pinned_words
 
 GRAPH_CACHE = 8                          # captured steps kept, oldest evicted first
 
@@ -62,20 +63,20 @@ class StepGraphs:
     def find(self, tr, batch, jitter_start, jitter_end, jitter_grad):
         """-> (key, cached step or None); key None: this step cannot be captured.  The steps whose staging pool was reallocated
         go first (Renderer._binned_workspace): the key is a live step's, or holds the capacities a capture would use now."""
-        r, t = tr.r, tr.t
+        r, t, sc = tr.r, tr.t, tr.r.counts
         self.cache = {k: rec for k, rec in self.cache.items() if rec.ws is r._bin_ws}
         if tr.use_graph is False or not r.field.flat.is_cuda or not tr.device_counts_ok() or \
-                r._spr is None or tr._dc_sync or (jitter_end is not None and jitter_start is None):
+                sc.spr is None or sc.host_repeat or (jitter_end is not None and jitter_start is None):
             return None, None
         B = batch["position"].shape[0]
         rays = [2 * B] + ([B] if t.w_grad > 0 else [])
-        caps = [r._capacities(n) for n in rays]
+        caps = [sc.capacities(n) for n in rays]
         if any(c is None for c in caps):
             return None, None
         sig = tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in batch.items() if isinstance(v, torch.Tensor)))
         shape = (B, float(tr.lr_scale), tr.grad_sampling_mode(), jitter_start is not None, jitter_grad is not None, sig,
                  t.train_contrast_threshold, t.train_refractory_period, float(t.w_grad))
-        key = pick_key(self.cache, caps, shape, rays, r._spr)
+        key = pick_key(self.cache, caps, shape, rays, sc.spr)
         return key, self.cache.get(key)
 
     def step(self, tr, batch, jitter_start, jitter_end, jitter_grad):
@@ -119,7 +120,7 @@ class StepGraphs:
         rec.graph.replay()
         tr.graph_replays += 1
         tr._ep_stale = True
-        if not tr._settle(rec.passes):               # (the step's aux is the first pass's)
+        if not tr.r.counts.settle(rec.passes):              # (the step's aux is the first pass's)
             if tr.world_size > 1:                    # (data parallelism: the graph ends where the gradient exchange begins)
                 tr._optimizer_after_passes(rec.aux)
             else:
@@ -131,7 +132,7 @@ class StepGraphs:
         tr._clear_grads()
         if tr.world_size == 1:
             tr._sync_hyper()
-        return tr._repeat_with_host_counts(lambda: tr._step_passes(batch, jitter_start, jitter_end, jitter_grad))
+        return tr.r.counts.repeat(tr, lambda: tr._step_passes(batch, jitter_start, jitter_end, jitter_grad))
 
     def _capture(self, tr, key, batch, jitter_start, jitter_grad) -> CapturedStep | None:
         from .engine import pack_batch
@@ -146,7 +147,7 @@ class StepGraphs:
             if r._bin_ws is None or r._bin_ws.numel() < ops.hashgrid_bwd_binned_workspace_bytes(need):
                 r._binned_workspace(2 * need, r.field.flat.device)
         _ = tr.side_stream
-        cap = Capture([torch.empty(4, dtype=torch.int64).pin_memory() for _ in key[0]])
+        cap = Capture([pinned_words() for _ in key[0]])
         # (a pool lives as long as a graph captured into it: an empty cache starts a new one -- torch asserts on a dead handle)
         if self.pool is None or not self.cache or os.environ.get("REN_STEP_GRAPH_POOL") == "own":
             self.pool = torch.cuda.graph_pool_handle()

@@ -135,7 +135,7 @@ def test_an_overflowed_pass_leaves_the_table_and_mlp_gradients_alone(amd, full_t
     run the loss passes ONCE with capacities four times too small and without the repeat (Trainer._forward_backward /
     _grad_loss_forward_backward directly, counts on the device) -- with and without the marcher's interval cache -- and look at the
     gradient buffers: the table and MLP gradients must still be exactly zero (only the 64-byte block of scalar-parameter gradients,
-    which _dc_pass restores from its snapshot, may have moved), and no per-sample array was written past its capacity (the step
+    which SampleCounts.run_pass restores from its snapshot, may have moved), and no per-sample array was written past its capacity (the step
     after it, with the capacities back, equals the host-count run)."""
     ops, engine = amd
     g = load_golden("training_step_grad")

@@ -9,7 +9,7 @@ from robust_e_nerf_amd import step_graph
 SHAPE = (2048, 1.0, "begun", True, True, (("position", (2048, 2), "torch.int64"),), False, False, 1e-3)
 RAYS, SPR = [4096, 2048], (40.0, 9.5)
 NEED = tuple(tuple(int(n * s * 1.08) + 1024 for s in SPR) for n in RAYS)
-FRESH = ((1 << 20, 1 << 18), (1 << 19, 1 << 17))          # what Renderer._capacities would give now
+FRESH = ((1 << 20, 1 << 18), (1 << 19, 1 << 17))          # what SampleCounts.capacities would give now
 
 
 def _pick(caps, shape=SHAPE):

@@ -69,7 +69,9 @@ int ren_abi_version(void);                       /* bumps when a signature chang
  *   REN_KNOB_HGB_HALVE_REGIONS 1: halve the bin regions so the overflow path (global atomics) runs
  *   REN_KNOB_MARCH_SEQUENTIAL  1: sequential occupancy marcher instead of the speculative one; 2 / 4 / 8 / 16: that many speculative
  *                              lanes per ray whatever the ray count (default: by ray count, csrc/ren_sampling.hip)
- *   REN_KNOB_HG_VARIANT        atomic hash-grid backward: bit 0 XCD-affine level mapping, bit 1 lane-pair atomics (default 2)
+ *   REN_KNOB_HG_VARIANT        atomic hash-grid backward: bit 0 XCD-affine level mapping, bit 1 lane-pair atomics (default 2);
+ *                              forward: bit 3 one workgroup row per level for the leading dense levels as well, instead of
+ *                              the one row that walks them all (the mapping before the fused dense row; same features)
  *   REN_KNOB_VFIELD_PLAIN      1: arch mlp, bf16 mode: the forward / backward kernels without the software-pipelined epilogue
  *   REN_KNOB_HGB_SUBREGION     binned scatter, which of a pair bin's 8 sub-regions a workgroup appends to: 1 (default) = the one
  *                              of the XCD it runs on, 0 = (workgroup index / 8) % 8, i.e. every sub-region written from all XCDs
@@ -133,6 +135,18 @@ int ren_ray_march(const float *rays_o, const float *rays_d, const float *t_min,
                   const int64_t *offsets, int32_t *counts,
                   int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
                   int32_t cache_cap, void *stream);
+/* The write pass of ren_ray_march (either mode) that stores every sample's unit-cube position beside the stream:
+ * x_unit[3 i ..] = contraction of `scene` applied to o + d (t0 + t1) / 2, the floats ren_hashgrid_fwd forms from the
+ * stream itself (same operations, same fused multiply-adds), so that the encoder can take x_unit instead and does not
+ * redo the ray fetch and the contraction once per level.  12 bytes per sample more in a launch that exists. */
+int ren_ray_march_unit(const float *rays_o, const float *rays_d, const float *t_min,
+                       const float *t_max, const float *jitter, int64_t n_rays,
+                       const float *roi_host, const int32_t *res_host, const uint8_t *binary,
+                       int32_t contraction_type, float step_size, float cone_angle,
+                       int32_t mode, int32_t n_uniform,
+                       const int64_t *offsets, int32_t *counts,
+                       int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
+                       int32_t cache_cap, const ren_scene_desc *scene, float *x_unit, void *stream);
 
 /* Exhaustive check behind REN_MARCH_VERIFIED_DIV: for each of the three extents b = roi[3 + k] - roi[k] (host floats, 2^-60 < b <
  * 2^60) every float a with 2^-100 < |a| < 2^100 is divided both ways -- a / b and q0 = a y, q = fma(fma(-q0, b, a), y, q0) with
@@ -180,6 +194,11 @@ int ren_compact_samples(const int64_t *offsets, const int32_t *counts, const int
                         int64_t n_rays, const uint8_t *keep, const float *t_starts,
                         const float *t_ends, int32_t *out_ray_indices, float *out_t_starts,
                         float *out_t_ends, void *stream);
+/* ... which moves the kept samples' unit positions (ren_ray_march_unit) with them: x_unit[3 n] -> out_x_unit[3 n_kept] */
+int ren_compact_samples_unit(const int64_t *offsets, const int32_t *counts, const int64_t *new_offsets,
+                             int64_t n_rays, const uint8_t *keep, const float *t_starts,
+                             const float *t_ends, const float *x_unit, int32_t *out_ray_indices, float *out_t_starts,
+                             float *out_t_ends, float *out_x_unit, void *stream);
 /* Fragment-layout features (32 floats per sample, see ren_hashgrid_fwd layout 1) of the kept samples, moved to
  * their compacted positions (same offsets/counts/new_offsets/keep as ren_compact_samples).  feat_out must hold
  * ceil(n_kept/32) blocks; the caller zeroes its last block (padding lanes). */
@@ -199,6 +218,11 @@ int ren_hashgrid_fwd(const ren_grid_desc *grid, const float *table, const float 
                      const ren_scene_desc *scene, const float *rays_o, const float *rays_d,
                      const int32_t *ray_indices, const float *t_starts, const float *t_ends,
                      int64_t n, int32_t layout, float *feat, const int64_t *n_dev, void *stream);
+/* x_unit[n,3] of a packed sample stream, as ren_hashgrid_fwd forms it from the stream: for streams whose writer did not
+ * store it (one streaming launch), and what the sampler's own x_unit is held to */
+int ren_unit_positions(const ren_scene_desc *scene, const float *rays_o, const float *rays_d,
+                       const int32_t *ray_indices, const float *t_starts, const float *t_ends, int64_t n,
+                       float *x_unit, const int64_t *n_dev, void *stream);
 /* d(table) += scatter of dfeat (same layouts); atomics, non-deterministic order */
 int ren_hashgrid_bwd(const ren_grid_desc *grid, float *grad_table, const float *x_unit,
                      const ren_scene_desc *scene, const float *rays_o, const float *rays_d,

@@ -44,6 +44,10 @@ SIGNATURES = {
     "ren_march_div_check": (c_int, [POINTER(c_float), P, P]),
     "ren_ray_march": (c_int, [P, P, P, P, P, c_int64, POINTER(c_float), POINTER(c_int32), P, c_int32,
                               c_float, c_float, c_int32, c_int32, P, P, P, P, P, P, c_int32, P]),
+    "ren_ray_march_unit": (c_int, [P, P, P, P, P, c_int64, POINTER(c_float), POINTER(c_int32), P, c_int32,
+                                   c_float, c_float, c_int32, c_int32, P, P, P, P, P, P, c_int32, POINTER(SceneDesc), P, P]),
+    "ren_compact_samples_unit": (c_int, [P, P, P, c_int64, P, P, P, P, P, P, P, P, P]),
+    "ren_unit_positions": (c_int, [POINTER(SceneDesc), P, P, P, P, P, c_int64, P, P, P]),
     "ren_compact_features": (c_int, [P, P, P, c_int64, P, P, P, P]),
     "ren_uniform": (c_int, [ctypes.c_uint64, ctypes.c_uint64, c_int64, P, P]),
     "ren_exclusive_scan": (c_int, [P, c_int64, P, P, P, P]),

@@ -67,8 +67,14 @@ static inline ren_scene_dev ren_make_scene(const ren_scene_desc *s) {
 }
 
 // World -> unit cube, robust_e_nerf/external/ngp.py:230-237 (+68-106).
+// (REN_FUSED_POSITIONS: defined by a translation unit that is compiled WITHOUT floating-point contraction -- the sampler's --
+// and stores unit positions for the encoder, whose translation unit contracts a * b + c into one FMA: in these two helpers
+// it then gets the same instructions, and the positions it stores are the floats the encoder would form itself)
 __device__ __forceinline__ void ren_contract(const ren_scene_dev &sc, float x, float y, float z,
                                              float &ux, float &uy, float &uz) {
+#ifdef REN_FUSED_POSITIONS
+#pragma clang fp contract(fast)
+#endif
     ux = (x - sc.lo[0]) / (sc.hi[0] - sc.lo[0]);
     uy = (y - sc.lo[1]) / (sc.hi[1] - sc.lo[1]);
     uz = (z - sc.lo[2]) / (sc.hi[2] - sc.lo[2]);
@@ -100,6 +106,28 @@ __device__ __forceinline__ void ren_sample_pos(const float *__restrict__ rays_o,
     x = o[0] + d[0] * tm;
     y = o[1] + d[1] * tm;
     z = o[2] + d[2] * tm;
+}
+
+// ... of a sample whose ray (origin, direction) and interval the caller holds: ren_sample_pos's expressions
+__device__ __forceinline__ void ren_sample_pos_at(const float *o, const float *d, float t0, float t1,
+                                                  float &x, float &y, float &z) {
+#ifdef REN_FUSED_POSITIONS
+#pragma clang fp contract(fast)
+#endif
+    float tm = (t0 + t1) * 0.5f;
+    x = o[0] + d[0] * tm;
+    y = o[1] + d[1] * tm;
+    z = o[2] + d[2] * tm;
+}
+
+// Unit-cube position of the sample (t0, t1) of a ray, stored as x_unit[3 at ..]: what the kernels that write the packed
+// sample stream add to it, so that the encoder reads 12 bytes per sample instead of redoing this for every level.
+__device__ __forceinline__ void ren_store_unit_pos(const ren_scene_dev &sc, const float *o, const float *d, float t0, float t1,
+                                                   float *__restrict__ x_unit, int64_t at) {
+    float x, y, z, ux, uy, uz;
+    ren_sample_pos_at(o, d, t0, t1, x, y, z);
+    ren_contract(sc, x, y, z, ux, uy, uz);
+    x_unit[3 * at] = ux; x_unit[3 * at + 1] = uy; x_unit[3 * at + 2] = uz;
 }
 
 // Device-side sample count (ABI 24, `n_dev` arguments): the host passes the CAPACITY of the per-sample arrays as `n` and, in

@@ -34,24 +34,31 @@ __device__ __forceinline__ bool block_to_work(int xcd_affine, int n_levels, int6
     return lvl < n_levels;
 }
 
+// Forward.  `n_fuse` > 1 (not with the XCD-affine mappings): blockIdx.y = 0 walks the n_fuse leading DENSE levels of its
+// samples one after the other -- together their slices fit one L2 (3.9 MB for the default grid), so nothing is gained by a
+// pass over the sample stream per level, and the position is loaded once for all of them -- and blockIdx.y = r >= 1 is the
+// level n_fuse + r - 1, one level per row as before.  Every level goes through the same arithmetic either way.
 template <int LAYOUT, bool FROM_RAYS>
 __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(
     GridDev g, const float2 *__restrict__ table, const float *__restrict__ x_unit, ren_scene_dev sc,
     const float *__restrict__ rays_o, const float *__restrict__ rays_d,
     const int32_t *__restrict__ ray_indices, const float *__restrict__ t_starts,
     const float *__restrict__ t_ends, int64_t n, int64_t n_pad, float *__restrict__ feat, int xcd_affine,
-    const int64_t *__restrict__ n_dev) {
+    const int64_t *__restrict__ n_dev, int n_fuse) {
     int lvl; int64_t chunk;
     if (!block_to_work(xcd_affine, g.n_levels, (n_pad + 255) / 256, lvl, chunk)) return;      // (the launch geometry is the capacity's)
+    int lvl_end = lvl + 1;
+    if (n_fuse > 1) {
+        if (lvl == 0) lvl_end = n_fuse; else { lvl += n_fuse - 1; lvl_end = lvl + 1; }
+    }
     const int64_t i = chunk * blockDim.x + threadIdx.x;
     if (n_dev) {                                             // device-side count: the fragment padding follows the real count
         n = ren_eff_n(n, n_dev);
         if (LAYOUT == 1) { const int64_t p = ((n + 31) >> 5) << 5; n_pad = p < n_pad ? p : n_pad; } else n_pad = n;
     }
     if (i >= n_pad) return;
-    float f0 = 0.f, f1 = 0.f;
+    float ux = 0.f, uy = 0.f, uz = 0.f;
     if (i < n) {
-        float ux, uy, uz;
         if (FROM_RAYS) {
             float x, y, z; int ray;
             ren_sample_pos(rays_o, rays_d, ray_indices, t_starts, t_ends, i, x, y, z, ray);
@@ -59,31 +66,52 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(
         } else {
             ux = x_unit[3 * i]; uy = x_unit[3 * i + 1]; uz = x_unit[3 * i + 2];
         }
-        const LevelPos p = level_pos(ux, uy, uz, g.scale[lvl]);
-        const uint32_t res = g.res[lvl], size = g.size[lvl];
-        const bool hashed = g.hashed[lvl] != 0;
-        const float2 *tab = table + g.offset[lvl];
-        float2 v[8];
-        uint32_t idx[8];
-        corner_indices8(p.c[0], p.c[1], p.c[2], res, size, hashed, idx);
-        gather_corners8(tab, idx, v);
+    }
+#pragma unroll 1
+    for (; lvl < lvl_end; ++lvl) {                           // (not unrolled: the register count of one level)
+        float f0 = 0.f, f1 = 0.f;
+        if (i < n) {
+            const LevelPos p = level_pos(ux, uy, uz, g.scale[lvl]);
+            const uint32_t res = g.res[lvl], size = g.size[lvl];
+            const bool hashed = g.hashed[lvl] != 0;
+            const float2 *tab = table + g.offset[lvl];
+            float2 v[8];
+            uint32_t idx[8];
+            corner_indices8(p.c[0], p.c[1], p.c[2], res, size, hashed, idx);
+            gather_corners8(tab, idx, v);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float wx = (c & 1) ? p.w[0] : 1.f - p.w[0];
-            const float wy = (c & 2) ? p.w[1] : 1.f - p.w[1];
-            const float wz = (c & 4) ? p.w[2] : 1.f - p.w[2];
-            const float w = wx * wy * wz;
-            f0 += w * v[c].x;
-            f1 += w * v[c].y;
+            for (int c = 0; c < 8; ++c) {
+                const float wx = (c & 1) ? p.w[0] : 1.f - p.w[0];
+                const float wy = (c & 2) ? p.w[1] : 1.f - p.w[1];
+                const float wz = (c & 4) ? p.w[2] : 1.f - p.w[2];
+                const float w = wx * wy * wz;
+                f0 += w * v[c].x;
+                f1 += w * v[c].y;
+            }
+        }
+        if (LAYOUT == 0) {
+            if (i < n) reinterpret_cast<float2 *>(feat)[i * g.n_levels + lvl] = make_float2(f0, f1);
+        } else {
+            const int64_t b = ((i >> 5) * REN_MAX_LEVELS + lvl) * 64 + (i & 31);
+            __builtin_nontemporal_store(f0, feat + b);       // streamed once: keep the level's table slice in L2 instead
+            __builtin_nontemporal_store(f1, feat + b + 32);
         }
     }
-    if (LAYOUT == 0) {
-        if (i < n) reinterpret_cast<float2 *>(feat)[i * g.n_levels + lvl] = make_float2(f0, f1);
-    } else {
-        const int64_t b = ((i >> 5) * REN_MAX_LEVELS + lvl) * 64 + (i & 31);
-        __builtin_nontemporal_store(f0, feat + b);           // streamed once: keep the level's table slice in L2 instead
-        __builtin_nontemporal_store(f1, feat + b + 32);
-    }
+}
+
+// unit-cube positions of a packed sample stream, as the ray-based encoder forms them (this translation unit's arithmetic)
+__global__ __launch_bounds__(256) void unit_positions_kernel(ren_scene_dev sc, const float *__restrict__ rays_o,
+                                                             const float *__restrict__ rays_d,
+                                                             const int32_t *__restrict__ ray_indices,
+                                                             const float *__restrict__ t_starts,
+                                                             const float *__restrict__ t_ends, int64_t n,
+                                                             const int64_t *__restrict__ n_dev, float *__restrict__ x_unit) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ren_eff_n(n, n_dev)) return;
+    float x, y, z, ux, uy, uz; int ray;
+    ren_sample_pos(rays_o, rays_d, ray_indices, t_starts, t_ends, i, x, y, z, ray);
+    ren_contract(sc, x, y, z, ux, uy, uz);
+    x_unit[3 * i] = ux; x_unit[3 * i + 1] = uy; x_unit[3 * i + 2] = uz;
 }
 
 template <int LAYOUT, bool FROM_RAYS, bool PAIR>
@@ -144,7 +172,8 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(
 }
 
 // Tuning knob (REN_KNOB_HG_VARIANT): bit 0 = XCD-affine level
-// mapping, bit 1 = lane-pair feature split in the backward kernel.
+// mapping, bit 1 = lane-pair feature split in the backward kernel, bit 3 = forward: one row per level for the leading
+// dense levels too (the mapping before the fused dense row).
 int hg_variant() { return ren_knob(REN_KNOB_HG_VARIANT); }
 
 }  // namespace
@@ -167,16 +196,31 @@ extern "C" int ren_hashgrid_fwd(const ren_grid_desc *grid, const float *table, c
     const int variant = hg_variant();
     const int affine = variant & 5;
     const int64_t n_chunks = (n_pad + 255) / 256;
+    int n_fuse = 0;                                          // leading dense levels, walked by the workgroups of row 0
+    if (!affine && !(variant & 8))
+        while (n_fuse < g.n_levels && !g.hashed[n_fuse]) ++n_fuse;
+    if (n_fuse < 2) n_fuse = 0;                              // none or one: the per-level mapping is the same thing
     dim3 grd = (affine & 4) ? dim3((unsigned)(g.n_levels * n_chunks))
-             : affine ? dim3((unsigned)(8 * ((g.n_levels + 7) / 8) * n_chunks)) : dim3((unsigned)n_chunks, g.n_levels);
+             : affine ? dim3((unsigned)(8 * ((g.n_levels + 7) / 8) * n_chunks))
+             : dim3((unsigned)n_chunks, n_fuse ? g.n_levels - n_fuse + 1 : g.n_levels);
     dim3 blk(256);
     const float2 *tab = reinterpret_cast<const float2 *>(table);
 #define LAUNCH(L, R)                                                                                     \
     hipLaunchKernelGGL((hashgrid_fwd_kernel<L, R>), grd, blk, 0, (hipStream_t)stream, g, tab, x_unit, sc, \
-                       rays_o, rays_d, ray_indices, t_starts, t_ends, n, n_pad, feat, affine, n_dev)
+                       rays_o, rays_d, ray_indices, t_starts, t_ends, n, n_pad, feat, affine, n_dev, n_fuse)
     if (layout == 0) { if (from_rays) LAUNCH(0, true); else LAUNCH(0, false); }
     else             { if (from_rays) LAUNCH(1, true); else LAUNCH(1, false); }
 #undef LAUNCH
+    REN_CHECK_LAUNCH();
+}
+
+extern "C" int ren_unit_positions(const ren_scene_desc *scene, const float *rays_o, const float *rays_d,
+                                  const int32_t *ray_indices, const float *t_starts, const float *t_ends, int64_t n,
+                                  float *x_unit, const int64_t *n_dev, void *stream) {
+    if (!scene || !rays_o || !rays_d || !ray_indices || !t_starts || !t_ends || !x_unit || n < 0) return REN_ERR_BAD_ARG;
+    if (n == 0) return REN_OK;
+    hipLaunchKernelGGL(unit_positions_kernel, dim3(ren_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, ren_make_scene(scene),
+                       rays_o, rays_d, ray_indices, t_starts, t_ends, n, n_dev, x_unit);
     REN_CHECK_LAUNCH();
 }
 

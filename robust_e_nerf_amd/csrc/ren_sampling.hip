@@ -6,6 +6,7 @@
 // un-fused float32 arithmetic so they match the sequential oracle (oracle/csrc/march.c) bit for
 // bit.  One thread per ray: rays are independent, the 2 MiB (128^3) / 16 MiB (256^3) occupancy
 // grid is L2 / Infinity-Cache resident, and the march is latency- not bandwidth-bound.
+#define REN_FUSED_POSITIONS                            // ren_common.h: the stored unit positions are the encoder's floats
 #include "ren_common.h"
 #include <cstdlib>
 
@@ -144,7 +145,8 @@ __global__ void ray_march_kernel(const float *__restrict__ o, const float *__res
                                  const uint8_t *__restrict__ binary,
                                  const int64_t *__restrict__ offsets, int32_t *__restrict__ counts,
                                  int32_t *__restrict__ ray_indices, float *__restrict__ t_starts,
-                                 float *__restrict__ t_ends, float2 *__restrict__ cache, int cache_cap) {
+                                 float *__restrict__ t_ends, float2 *__restrict__ cache, int cache_cap,
+                                 ren_scene_dev sc, float *__restrict__ x_unit) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rays) return;
     // write pass with an interval cache: rays whose intervals the count pass kept are copied by
@@ -169,6 +171,7 @@ __global__ void ray_march_kernel(const float *__restrict__ o, const float *__res
                     t_starts[base + j] = t0;
                     t_ends[base + j] = t0 + delta;
                     ray_indices[base + j] = (int32_t)i;
+                    if (x_unit) ren_store_unit_pos(sc, ro, rd, t0, t0 + delta, x_unit, base + j);
                 }
             }
             j = a.n_uniform;
@@ -191,6 +194,7 @@ __global__ void ray_march_kernel(const float *__restrict__ o, const float *__res
                 t_starts[base + j] = t0;
                 t_ends[base + j] = t1;
                 ray_indices[base + j] = (int32_t)i;
+                if (x_unit) ren_store_unit_pos(sc, ro, rd, t0, t1, x_unit, base + j);
             } else if (cache && j < cache_cap) {
                 cache[i * cache_cap + j] = make_float2(t0, t1);
             }
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(256) void ray_march_spec_kernel(
     const float *__restrict__ t_max, const float *__restrict__ jitter, int64_t n_rays, MarchArgs a,
     const uint8_t *__restrict__ binary, const int64_t *__restrict__ offsets, int32_t *__restrict__ counts,
     int32_t *__restrict__ ray_indices, float *__restrict__ t_starts, float *__restrict__ t_ends,
-    float2 *__restrict__ cache, int cache_cap) {
+    float2 *__restrict__ cache, int cache_cap, ren_scene_dev sc, float *__restrict__ x_unit) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / SPEC;
     const int l = threadIdx.x % SPEC, lane = threadIdx.x & 63, g0 = lane - l;   // g0: first lane of the group
     bool done = i >= n_rays;
@@ -328,6 +332,7 @@ __global__ __launch_bounds__(256) void ray_march_spec_kernel(
                 t_starts[base + at] = a0;
                 t_ends[base + at] = a1;
                 ray_indices[base + at] = (int32_t)i;
+                if (x_unit) ren_store_unit_pos(sc, ro, rd, a0, a1, x_unit, base + at);
             } else if (cache && at < cache_cap) {
                 cache[i * cache_cap + at] = make_float2(a0, a1);
             }
@@ -359,7 +364,9 @@ __global__ __launch_bounds__(256) void cached_write_kernel(const float2 *__restr
                                                            const int64_t *__restrict__ offsets,
                                                            const int32_t *__restrict__ counts,
                                                            int32_t *__restrict__ ray_indices, float *__restrict__ t_starts,
-                                                           float *__restrict__ t_ends) {
+                                                           float *__restrict__ t_ends, const float *__restrict__ o,
+                                                           const float *__restrict__ d, ren_scene_dev sc,
+                                                           float *__restrict__ x_unit) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = g >> 3;
     if (i >= n_rays) return;
@@ -367,11 +374,17 @@ __global__ __launch_bounds__(256) void cached_write_kernel(const float2 *__restr
     if (c > cache_cap) return;
     const int64_t base = offsets[i];
     const float2 *src = cache + i * cache_cap;
+    float ro[3] = {0.f, 0.f, 0.f}, rd[3] = {0.f, 0.f, 0.f};
+    if (x_unit) {                                                  // once per ray
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ro[k] = o[3 * i + k]; rd[k] = d[3 * i + k]; }
+    }
     for (int j = (int)(g & 7); j < c; j += 8) {
         const float2 v = src[j];
         t_starts[base + j] = v.x;
         t_ends[base + j] = v.y;
         ray_indices[base + j] = (int32_t)i;
+        if (x_unit) ren_store_unit_pos(sc, ro, rd, v.x, v.y, x_unit, base + j);
     }
 }
 
@@ -382,7 +395,9 @@ __global__ __launch_bounds__(256) void uniform_write_kernel(const float *__restr
                                                             const float *__restrict__ jitter, int64_t n_rays, int n_uniform,
                                                             const int64_t *__restrict__ offsets,
                                                             int32_t *__restrict__ ray_indices, float *__restrict__ t_starts,
-                                                            float *__restrict__ t_ends) {
+                                                            float *__restrict__ t_ends, const float *__restrict__ o,
+                                                            const float *__restrict__ d, ren_scene_dev sc,
+                                                            float *__restrict__ x_unit) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = g / n_uniform;
     const int j = (int)(g - i * n_uniform);
@@ -396,6 +411,10 @@ __global__ __launch_bounds__(256) void uniform_write_kernel(const float *__restr
     t_starts[at] = t0;
     t_ends[at] = t0 + delta;
     ray_indices[at] = (int32_t)i;
+    if (x_unit) {                                                  // (a wave's lanes share one or two rays: broadcast loads)
+        const float ro[3] = {o[3 * i], o[3 * i + 1], o[3 * i + 2]}, rd[3] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+        ren_store_unit_pos(sc, ro, rd, t0, t0 + delta, x_unit, at);
+    }
 }
 
 // Exclusive scan of the per-ray sample counts, up to SCAN_TILE * 1024 elements, in three coalesced stages:
@@ -514,7 +533,8 @@ __global__ __launch_bounds__(256) void compact_kernel(const int64_t *__restrict_
                                const int64_t *__restrict__ new_offsets, int64_t n_rays,
                                const uint8_t *__restrict__ keep, const float *__restrict__ t_starts,
                                const float *__restrict__ t_ends, int32_t *__restrict__ out_ri,
-                               float *__restrict__ out_ts, float *__restrict__ out_te) {
+                               float *__restrict__ out_ts, float *__restrict__ out_te,
+                               const float *__restrict__ x_unit, float *__restrict__ out_xu) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (i >= n_rays) return;
@@ -531,6 +551,10 @@ __global__ __launch_bounds__(256) void compact_kernel(const int64_t *__restrict_
             out_ri[at] = (int32_t)i;
             out_ts[at] = t_starts[j];
             out_te[at] = t_ends[j];
+            if (out_xu) {                                          // the survivors' unit positions move with them
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out_xu[3 * at + k] = x_unit[3 * j + k];
+            }
         }
         w += __popcll(m);
     }
@@ -646,14 +670,17 @@ extern "C" int ren_march_div_check(const float *roi, int64_t *mismatches, void *
     REN_CHECK_LAUNCH();
 }
 
-extern "C" int ren_ray_march(const float *rays_o, const float *rays_d, const float *t_min,
-                             const float *t_max, const float *jitter, int64_t n_rays,
-                             const float *roi, const int32_t *res, const uint8_t *binary,
-                             int32_t contraction_type, float step_size, float cone_angle,
-                             int32_t mode, int32_t n_uniform, const int64_t *offsets, int32_t *counts,
-                             int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
-                             int32_t cache_cap, void *stream) {
+static int ray_march_impl(const float *rays_o, const float *rays_d, const float *t_min,
+                          const float *t_max, const float *jitter, int64_t n_rays,
+                          const float *roi, const int32_t *res, const uint8_t *binary,
+                          int32_t contraction_type, float step_size, float cone_angle,
+                          int32_t mode, int32_t n_uniform, const int64_t *offsets, int32_t *counts,
+                          int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
+                          int32_t cache_cap, const ren_scene_desc *scene, float *x_unit, void *stream) {
     if (!rays_o || !rays_d || !t_min || !t_max || n_rays < 0) return REN_ERR_BAD_ARG;
+    if (x_unit && (!scene || !t_starts)) return REN_ERR_BAD_ARG;        // unit positions go with a WRITE pass
+    ren_scene_dev sc = {};
+    if (scene) sc = ren_make_scene(scene);
     const bool verified_div = (mode & REN_MARCH_VERIFIED_DIV) != 0;
     mode &= ~REN_MARCH_VERIFIED_DIV;
     if (mode != 0 && mode != 1) return REN_ERR_BAD_ARG;
@@ -689,42 +716,69 @@ extern "C" int ren_ray_march(const float *rays_o, const float *rays_d, const flo
         if (width == 16)                                                                                                   \
             hipLaunchKernelGGL((ray_march_spec_kernel<WRITE, 16>), sgrid, dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, \
                                t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices, t_starts, t_ends,    \
-                               cache, cache_cap);                                                                          \
+                               cache, cache_cap, sc, x_unit);                                                              \
         else if (width == 8)                                                                                               \
             hipLaunchKernelGGL((ray_march_spec_kernel<WRITE, 8>), sgrid, dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, \
                                t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices, t_starts, t_ends,    \
-                               cache, cache_cap);                                                                          \
+                               cache, cache_cap, sc, x_unit);                                                              \
         else if (width == 4)                                                                                               \
             hipLaunchKernelGGL((ray_march_spec_kernel<WRITE, 4>), sgrid, dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, \
                                t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices, t_starts, t_ends,    \
-                               cache, cache_cap);                                                                          \
+                               cache, cache_cap, sc, x_unit);                                                              \
         else                                                                                                               \
             hipLaunchKernelGGL((ray_march_spec_kernel<WRITE, 2>), sgrid, dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, \
                                t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices, t_starts, t_ends,    \
-                               cache, cache_cap);                                                                          \
+                               cache, cache_cap, sc, x_unit);                                                              \
     } while (0)
     if (write && mode == 1)
         hipLaunchKernelGGL(uniform_write_kernel, dim3(ren_blocks(n_rays * n_uniform, 256)), dim3(256), 0,
                            (hipStream_t)stream, t_min, t_max, jitter, n_rays, n_uniform, offsets, ray_indices,
-                           t_starts, t_ends);
+                           t_starts, t_ends, rays_o, rays_d, sc, x_unit);
     else if (write) {
         if (cache)
             hipLaunchKernelGGL(cached_write_kernel, dim3(ren_blocks(n_rays * 8, 256)), dim3(256), 0, (hipStream_t)stream,
-                               cache, cache_cap, n_rays, offsets, counts, ray_indices, t_starts, t_ends);
+                               cache, cache_cap, n_rays, offsets, counts, ray_indices, t_starts, t_ends, rays_o, rays_d, sc,
+                               x_unit);
         if (width)
             REN_MARCH_SPEC(true);
         else
             hipLaunchKernelGGL(ray_march_kernel<true>, grid, block, 0, (hipStream_t)stream, rays_o, rays_d,
                                t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices,
-                               t_starts, t_ends, cache, cache_cap);
+                               t_starts, t_ends, cache, cache_cap, sc, x_unit);
     } else if (width)
         REN_MARCH_SPEC(false);
     else
         hipLaunchKernelGGL(ray_march_kernel<false>, grid, block, 0, (hipStream_t)stream, rays_o, rays_d,
                            t_min, t_max, jitter, n_rays, a, binary, offsets, counts, ray_indices,
-                           t_starts, t_ends, cache, cache_cap);
+                           t_starts, t_ends, cache, cache_cap, sc, x_unit);
 #undef REN_MARCH_SPEC
     REN_CHECK_LAUNCH();
+}
+
+extern "C" int ren_ray_march(const float *rays_o, const float *rays_d, const float *t_min,
+                             const float *t_max, const float *jitter, int64_t n_rays,
+                             const float *roi, const int32_t *res, const uint8_t *binary,
+                             int32_t contraction_type, float step_size, float cone_angle,
+                             int32_t mode, int32_t n_uniform, const int64_t *offsets, int32_t *counts,
+                             int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
+                             int32_t cache_cap, void *stream) {
+    return ray_march_impl(rays_o, rays_d, t_min, t_max, jitter, n_rays, roi, res, binary, contraction_type, step_size,
+                          cone_angle, mode, n_uniform, offsets, counts, ray_indices, t_starts, t_ends, interval_cache,
+                          cache_cap, nullptr, nullptr, stream);
+}
+
+// the write pass of ren_ray_march that also stores every sample's unit-cube position (x_unit[3 n], `scene`'s contraction)
+extern "C" int ren_ray_march_unit(const float *rays_o, const float *rays_d, const float *t_min,
+                                  const float *t_max, const float *jitter, int64_t n_rays,
+                                  const float *roi, const int32_t *res, const uint8_t *binary,
+                                  int32_t contraction_type, float step_size, float cone_angle,
+                                  int32_t mode, int32_t n_uniform, const int64_t *offsets, int32_t *counts,
+                                  int32_t *ray_indices, float *t_starts, float *t_ends, float *interval_cache,
+                                  int32_t cache_cap, const ren_scene_desc *scene, float *x_unit, void *stream) {
+    if (!scene || !x_unit || !t_starts) return REN_ERR_BAD_ARG;
+    return ray_march_impl(rays_o, rays_d, t_min, t_max, jitter, n_rays, roi, res, binary, contraction_type, step_size,
+                          cone_angle, mode, n_uniform, offsets, counts, ray_indices, t_starts, t_ends, interval_cache,
+                          cache_cap, scene, x_unit, stream);
 }
 
 // ---- uniform random numbers for the stratified-sampling jitter (models/nerf.py passes torch.rand; any iid U[0,1) stream is
@@ -928,19 +982,39 @@ extern "C" int ren_visibility(const int64_t *offsets, const int32_t *counts, int
     REN_CHECK_LAUNCH();
 }
 
-extern "C" int ren_compact_samples(const int64_t *offsets, const int32_t *counts,
-                                   const int64_t *new_offsets, int64_t n_rays, const uint8_t *keep,
-                                   const float *t_starts, const float *t_ends,
-                                   int32_t *out_ray_indices, float *out_t_starts, float *out_t_ends,
-                                   void *stream) {
+static int compact_samples_impl(const int64_t *offsets, const int32_t *counts,
+                                const int64_t *new_offsets, int64_t n_rays, const uint8_t *keep,
+                                const float *t_starts, const float *t_ends,
+                                int32_t *out_ray_indices, float *out_t_starts, float *out_t_ends,
+                                const float *x_unit, float *out_x_unit, void *stream) {
     if (!offsets || !counts || !new_offsets || !keep || !t_starts || !t_ends || !out_ray_indices ||
         !out_t_starts || !out_t_ends || n_rays < 0)
         return REN_ERR_BAD_ARG;
     if (n_rays == 0) return REN_OK;
     hipLaunchKernelGGL(compact_kernel, dim3(ren_blocks(n_rays * 64, 256)), dim3(256), 0, (hipStream_t)stream,
                        offsets, counts, new_offsets, n_rays, keep, t_starts, t_ends, out_ray_indices,
-                       out_t_starts, out_t_ends);
+                       out_t_starts, out_t_ends, x_unit, out_x_unit);
     REN_CHECK_LAUNCH();
+}
+
+extern "C" int ren_compact_samples(const int64_t *offsets, const int32_t *counts,
+                                   const int64_t *new_offsets, int64_t n_rays, const uint8_t *keep,
+                                   const float *t_starts, const float *t_ends,
+                                   int32_t *out_ray_indices, float *out_t_starts, float *out_t_ends,
+                                   void *stream) {
+    return compact_samples_impl(offsets, counts, new_offsets, n_rays, keep, t_starts, t_ends, out_ray_indices, out_t_starts,
+                                out_t_ends, nullptr, nullptr, stream);
+}
+
+// ren_compact_samples that moves the kept samples' unit positions (x_unit[3 n] -> out_x_unit[3 n_new]) as well
+extern "C" int ren_compact_samples_unit(const int64_t *offsets, const int32_t *counts,
+                                        const int64_t *new_offsets, int64_t n_rays, const uint8_t *keep,
+                                        const float *t_starts, const float *t_ends, const float *x_unit,
+                                        int32_t *out_ray_indices, float *out_t_starts, float *out_t_ends,
+                                        float *out_x_unit, void *stream) {
+    if (!x_unit || !out_x_unit) return REN_ERR_BAD_ARG;
+    return compact_samples_impl(offsets, counts, new_offsets, n_rays, keep, t_starts, t_ends, out_ray_indices, out_t_starts,
+                                out_t_ends, x_unit, out_x_unit, stream);
 }
 
 extern "C" int ren_compact_features(const int64_t *offsets, const int32_t *counts, const int64_t *new_offsets,

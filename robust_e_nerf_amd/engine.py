@@ -201,6 +201,8 @@ class Packed:
     n_dev: Optional[torch.Tensor] = None        # device-side counts: `n` is then the CAPACITY of the arrays (it sizes the launches),
                                                 # the number of samples that exist is n_dev[0] (int64 on the device)
     log: Optional["CountLog"] = None            # where the host will find the counts (and whether they fitted)
+    x_unit: Optional[torch.Tensor] = None       # (n, 3) unit-cube positions of these samples, stored by the kernel that wrote the
+                                                # stream: the encoder reads them instead of redoing ray fetch + contraction per level
 
 
 def pack_batch(batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -367,6 +369,10 @@ class Renderer:
         return (c.device_counts is not False and c.sampler == "occgrid" and type(self) is Renderer and c.mlp_kernels == "x" and
                 c.binned_scatter and self.field.flat.is_cuda)
 
+    def _unit_scene(self):
+        """the scene whose contraction the sampler's write kernels apply for Packed.x_unit, or None: the hash-grid field only"""
+        return self.scene if (type(self) is Renderer and getattr(self.field, "grid", None) is not None) else None
+
     def _sample_device_counts(self, o, d, st, caps, keep_feat: bool) -> Packed:
         """sample() without a host read: both counts stay on the device, every array has a capacity, two guards clear the
         render (and report it) should a count not fit"""
@@ -379,18 +385,21 @@ class Renderer:
             ops.count_guard(counts, st["total"], caps[0], nd[0:1], stats[0:2])
         cap0, cap1 = caps
         n0_dev, n1_dev = nd[0:1], nd[1:2]
-        ri, ts, te = ops.ray_march_write(*args, offsets, cap0, counts=counts, cache=cache)
+        ri, ts, te, *xu = ops.ray_march_write(*args, offsets, cap0, counts=counts, cache=cache, unit_scene=self._unit_scene())
+        xu = xu[0] if xu else None
         keep_feat = keep_feat and self._reuse_prepass_feat
-        sigma = self._density_stream(o, d, (ri, ts, te), cap0, keep_feat, n_dev=n0_dev)
+        sigma = self._density_stream(o, d, (ri, ts, te), cap0, keep_feat, n_dev=n0_dev, x_unit=xu)
         feat0 = None
         if keep_feat:
             sigma, feat0 = sigma
         keep, kept = ops.visibility(offsets, counts, sigma, ts, te, c.early_stop_eps, c.alpha_thre)
         new_offsets, total2 = ops.scan_guard(kept, cap1, n1_dev, stats[2:4], counts_also=counts)
-        ri2, ts2, te2 = ops.compact_samples(offsets, counts, new_offsets, keep, ts, te, cap1)
+        # (the survivors' positions move with them only when the differentiable pass will encode them again)
+        ri2, ts2, te2, *xu2 = ops.compact_samples(offsets, counts, new_offsets, keep, ts, te, cap1,
+                                                  x_unit=xu if feat0 is None else None)
         feat1 = ops.compact_features(offsets, counts, new_offsets, keep, feat0, cap1, n_dev=n1_dev) if feat0 is not None else None
         log = self.counts.log(o.shape[0], caps, stats, self._capture)
-        return Packed(ri2, ts2, te2, new_offsets, kept, cap1, cap0, feat1, n_dev=n1_dev, log=log)
+        return Packed(ri2, ts2, te2, new_offsets, kept, cap1, cap0, feat1, n_dev=n1_dev, log=log, x_unit=xu2[0] if xu2 else None)
 
     def sample(self, o, d, jitter: Optional[torch.Tensor], training: bool, keep_feat: bool = False,
                begun: Optional[dict] = None, device_counts=False) -> Packed:
@@ -409,27 +418,30 @@ class Renderer:
                 return self._sample_device_counts(o, d, st, caps, keep_feat)
         # host sync, as in the reference (external/utils.py:106-119); `begun["n0"]`: already read back (Trainer.prefetch)
         n0 = st["n0"] if "n0" in st else _host_int(st["total"])
-        ri, ts, te = ops.ray_march_write(*args, offsets, n0, counts=counts, cache=cache)
+        ri, ts, te, *xu = ops.ray_march_write(*args, offsets, n0, counts=counts, cache=cache, unit_scene=self._unit_scene())
+        xu = xu[0] if xu else None
         if mode == 1 or n0 == 0:
             if learn:
                 self.counts.learn(o.shape[0], n0, n0)
-            return Packed(ri, ts, te, offsets, counts, n0, n0)
+            return Packed(ri, ts, te, offsets, counts, n0, n0, x_unit=xu)
         # sigma_fn pre-pass (external/utils.py:68-81) + render_visibility
         keep_feat = keep_feat and self._reuse_prepass_feat and c.mlp_kernels == "x"
-        sigma = self._density_stream(o, d, (ri, ts, te), n0, keep_feat)
+        sigma = self._density_stream(o, d, (ri, ts, te), n0, keep_feat, **({} if xu is None else dict(x_unit=xu)))
         feat0 = None
         if keep_feat:
             sigma, feat0 = sigma
         keep, kept = ops.visibility(offsets, counts, sigma, ts, te, c.early_stop_eps, c.alpha_thre)
         new_offsets, total2 = ops.exclusive_scan(kept)
         n1 = _host_int(total2)
-        ri2, ts2, te2 = ops.compact_samples(offsets, counts, new_offsets, keep, ts, te, n1)
+        # (the survivors' positions move with them only when the differentiable pass will encode them again)
+        ri2, ts2, te2, *xu2 = ops.compact_samples(offsets, counts, new_offsets, keep, ts, te, n1,
+                                                  x_unit=xu if feat0 is None else None)
         feat1 = None
         if feat0 is not None and n1 > 0:                     # the pre-pass already encoded every survivor
             feat1 = feat0 if n1 == n0 else ops.compact_features(offsets, counts, new_offsets, keep, feat0, n1)
         if learn:
             self.counts.learn(o.shape[0], n0, n1)
-        return Packed(ri2, ts2, te2, new_offsets, kept, n1, n0, feat1)
+        return Packed(ri2, ts2, te2, new_offsets, kept, n1, n0, feat1, x_unit=xu2[0] if xu2 else None)
 
     # ---- field evaluation over a packed sample stream (overridden by vanilla.VanillaRenderer) ----------
     def _mlp_params(self):
@@ -438,9 +450,15 @@ class Renderer:
         m = self.field.mlp
         return m.to(torch.bfloat16).to(torch.float32) if self.cfg.mlp_bf16 else m
 
-    def _density_stream(self, o, d, samples, n, return_feat: bool = False, n_dev=None):
-        feat = ops.hashgrid_fwd(self.field.grid, self.field.table, scene=self.scene, rays=(o, d),
-                                samples=samples, n=n, layout=1, n_dev=n_dev)
+    def _hash_features(self, o, d, samples, n, x_unit=None, n_dev=None, out=None):
+        """hash features (fragment order) of a packed sample stream: from its stored unit positions when it has them"""
+        f = self.field
+        if x_unit is not None:
+            return ops.hashgrid_fwd(f.grid, f.table, x_unit=x_unit, n=n, layout=1, n_dev=n_dev, out=out)
+        return ops.hashgrid_fwd(f.grid, f.table, scene=self.scene, rays=(o, d), samples=samples, n=n, layout=1, n_dev=n_dev, out=out)
+
+    def _density_stream(self, o, d, samples, n, return_feat: bool = False, n_dev=None, x_unit=None):
+        feat = self._hash_features(o, d, samples, n, x_unit=x_unit, n_dev=n_dev)
         if self.cfg.mlp_kernels == "x":
             _, sigma, _, _ = ops.mlp_fwd_x(self.field.mlp, self.field.C, self._xmode(), feat, self.scene, rays=(o, d),
                                            samples=samples, n=n, density_only=True, act=self._act_code, n_dev=n_dev)
@@ -486,8 +504,7 @@ class Renderer:
         chunks = min(self.cfg.fwd_chunks, pk.n >> 20) if pk.n >= (1 << 23) else 1   # pays from ~8 M samples, >= 1 M per chunk
         if self.cfg.mlp_kernels == "x" and chunks > 1 and pk.feat is None and pk.n_dev is None:
             return self._field_forward_chunked(o, d, pk, save, chunks)
-        feat = pk.feat if pk.feat is not None else \
-            ops.hashgrid_fwd(f.grid, f.table, scene=self.scene, rays=(o, d), samples=samples, n=pk.n, layout=1, n_dev=pk.n_dev)
+        feat = pk.feat if pk.feat is not None else self._hash_features(o, d, samples, pk.n, x_unit=pk.x_unit, n_dev=pk.n_dev)
         if self.cfg.mlp_kernels == "x":
             rgb, sigma, base, acts = ops.mlp_fwd_x(f.mlp, f.C, self._xmode(), feat, self.scene, rays=(o, d), samples=samples,
                                                    n=pk.n, save=save, save_acts=self._save_acts(), act=self._act_code, n_dev=pk.n_dev)
@@ -529,7 +546,7 @@ class Renderer:
             smp = (pk.ray_indices[lo:hi], pk.t_starts[lo:hi], pk.t_ends[lo:hi])
             fk = feat[b0 * ops.FRAG_FLOATS_PER_BLOCK: b1 * ops.FRAG_FLOATS_PER_BLOCK]
             with torch.cuda.stream(s_enc):
-                ops.hashgrid_fwd(f.grid, f.table, scene=self.scene, rays=(o, d), samples=smp, n=hi - lo, layout=1, out=fk)
+                self._hash_features(o, d, smp, hi - lo, x_unit=None if pk.x_unit is None else pk.x_unit[lo:hi], out=fk)
                 ev = torch.cuda.Event()
                 ev.record(s_enc)
             with torch.cuda.stream(s_mlp):

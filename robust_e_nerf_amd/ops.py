@@ -267,7 +267,8 @@ def ray_march_count(o, d, t_min, t_max, jitter, roi, res, binary, ct, step, cone
 
 
 def ray_march_write(o, d, t_min, t_max, jitter, roi, res, binary, ct, step, cone, mode, n_uniform,
-                    offsets, n_total: int, out=None, counts=None, cache=None):
+                    offsets, n_total: int, out=None, counts=None, cache=None, unit_scene: Optional[SceneDesc] = None):
+    """unit_scene: the launch also stores the samples' unit-cube positions (ren_ray_march_unit) -> (ri, ts, te, x_unit)"""
     n = o.shape[0]
     if out is None:
         ri = torch.empty(n_total, device=o.device, dtype=torch.int32)
@@ -275,17 +276,32 @@ def ray_march_write(o, d, t_min, t_max, jitter, roi, res, binary, ct, step, cone
         te = torch.empty(n_total, device=o.device, dtype=torch.float32)
     else:
         ri, ts, te = out
+    xu = torch.empty(n_total, 3, device=o.device, dtype=torch.float32) if unit_scene is not None else None
+    ret = (ri, ts, te) if xu is None else (ri, ts, te, xu)
     if n_total == 0:                                  # no ray meets an occupied cell: nothing to write
-        return ri, ts, te
+        return ret
     roi_c = (ctypes.c_float * 6)(*[float(v) for v in roi])
     res_c = (ctypes.c_int32 * 3)(*[int(v) for v in res])
-    check(_lib.load().ren_ray_march(_ptr(o), _ptr(d), _ptr(t_min), _ptr(t_max), _ptr(jitter), n, roi_c, res_c,
-                                    _ptr(binary, (torch.uint8, torch.bool)), ct, _f(step), _f(cone), mode, n_uniform,
-                                    _ptr(offsets, torch.int64), _ptr(counts, torch.int32), _ptr(ri), _ptr(ts), _ptr(te),
-                                    _ptr(cache, torch.float32) if counts is not None else None,
-                                    0 if (cache is None or counts is None) else cache.shape[1], _stream()),
-          "ren_ray_march(write)")
-    return ri, ts, te
+    args = (_ptr(o), _ptr(d), _ptr(t_min), _ptr(t_max), _ptr(jitter), n, roi_c, res_c,
+            _ptr(binary, (torch.uint8, torch.bool)), ct, _f(step), _f(cone), mode, n_uniform,
+            _ptr(offsets, torch.int64), _ptr(counts, torch.int32), _ptr(ri), _ptr(ts), _ptr(te),
+            _ptr(cache, torch.float32) if counts is not None else None,
+            0 if (cache is None or counts is None) else cache.shape[1])
+    if xu is None:
+        check(_lib.load().ren_ray_march(*args, _stream()), "ren_ray_march(write)")
+    else:
+        check(_lib.load().ren_ray_march_unit(*args, ctypes.byref(unit_scene), _ptr(xu), _stream()), "ren_ray_march_unit")
+    return ret
+
+
+def unit_positions(scene: SceneDesc, rays, samples, n: int, n_dev=None, out=None):
+    """(n, 3) unit-cube positions of a packed sample stream, as hashgrid_fwd forms them from the stream itself"""
+    (o, d), (ri, ts, te) = rays, samples
+    if out is None:
+        out = torch.empty(n, 3, device=o.device, dtype=torch.float32)
+    check(_lib.load().ren_unit_positions(ctypes.byref(scene), _ptr(o), _ptr(d), _ptr(ri, torch.int32), _ptr(ts), _ptr(te), n,
+                                         _ptr(out, torch.float32), _ptr(n_dev, torch.int64), _stream()), "ren_unit_positions")
+    return out
 
 
 def count_guard(counts, total, capacity: int, n_out, stats=None, counts_also=None):
@@ -323,11 +339,19 @@ def visibility(offsets, counts, sigmas, ts, te, eps: float, alpha_thre: float):
     return keep, kept
 
 
-def compact_samples(offsets, counts, new_offsets, keep, ts, te, n_new: int):
+def compact_samples(offsets, counts, new_offsets, keep, ts, te, n_new: int, x_unit=None):
+    """x_unit: the samples' unit positions (ray_march_write(unit_scene=...)) are compacted with them -> (ri, ts, te, x_unit)"""
     n_rays = counts.shape[0]
     ri2 = torch.empty(n_new, device=ts.device, dtype=torch.int32)
     ts2 = torch.empty(n_new, device=ts.device, dtype=torch.float32)
     te2 = torch.empty(n_new, device=ts.device, dtype=torch.float32)
+    if x_unit is not None:
+        xu2 = torch.empty(n_new, 3, device=ts.device, dtype=torch.float32)
+        if n_new > 0:
+            check(_lib.load().ren_compact_samples_unit(_ptr(offsets), _ptr(counts), _ptr(new_offsets), n_rays, _ptr(keep),
+                                                       _ptr(ts), _ptr(te), _ptr(x_unit, torch.float32), _ptr(ri2), _ptr(ts2),
+                                                       _ptr(te2), _ptr(xu2), _stream()), "ren_compact_samples_unit")
+        return ri2, ts2, te2, xu2
     if n_new == 0:                                    # everything culled by the visibility test
         return ri2, ts2, te2
     check(_lib.load().ren_compact_samples(_ptr(offsets), _ptr(counts), _ptr(new_offsets), n_rays, _ptr(keep),

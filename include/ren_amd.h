@@ -866,6 +866,30 @@ int ren_event_table_write(const uint8_t *valid, const int32_t *offsets, const vo
                           int64_t *out_start_ts, int64_t *out_end_ts, int64_t *out_num_pos, int64_t *out_num_neg,
                           uint8_t *out_channel_idx, void *stream);
 
+/* ---- event filter (csrc/ren_event_filter.hip) --------------------------------------------------------- *
+ * Which events of a raw stream (x, y, t) on a W x H sensor are scene signal.  Polarity plays no part.
+ * Event e at pixel (x, y) and time t is SUPPORTED iff there is an event e' != e at an in-sensor pixel (x', y') with
+ * max(|x - x'|, |y - y'|) <= 1 that is not hot and is not (x, y) itself unless include_self, with 0 <= t - t' <= dt: ties count
+ * (two neighbours with one timestamp support each other), t - t' = dt counts, dt + 1 does not.  keep(e) = (the pixel of e is
+ * not hot) and supported(e).  The definition names no stream order: keep is a function of the multiset of events and repeats
+ * bit for bit.
+ * ren_event_support: pix_sorted (N int32 keys y * W + x in stable by-pixel order) and order (N int64, the stream index of each
+ * sorted slot, a permutation of 0 .. N - 1) as for "event table"; ts_sorted (N int64): the timestamps IN THE SORTED ORDER,
+ * non-decreasing inside every pixel's segment (they are when the stream is time-ordered: the CALLER checks that); seg
+ * (H * W + 1 int32): seg[p] = the first sorted slot of pixel p, seg[H * W] = N; hot (H * W uint8, != 0 = hot; NULL = no pixel
+ * is hot); dt >= 0, or dt < 0 for "every event is supported" (keep = not hot); include_self 0 or 1.  keep (N uint8, STREAM
+ * order): keep[order[i]] for every sorted slot i, each stream index written exactly once.  One launch, one slot per lane per
+ * trip of a grid-stride loop; per neighbour pixel a binary search of its segment for the last t' <= t.  Time differences are
+ * signed 64-bit.  An order entry outside [0, N) is skipped (nothing read or written); a key outside [0, H * W) is not kept; segment
+ * bounds are clamped to [0, N] before use.  No LDS, no atomics, no workgroup waits on another.
+ * REN_ERR_BAD_ARG before any launch for a null or misaligned required pointer, N < 0, H or W < 1, include_self other than 0 / 1;
+ * REN_ERR_UNSUPPORTED for N or H * W >= 2^31; N == 0 launches nothing. */
+#define REN_EVENT_FILTER_THREADS 256         /* workgroup size */
+#define REN_EVENT_FILTER_MAX_BLOCKS 2048     /* at most this many workgroups; the grid-stride loop takes the rest */
+int ren_event_support(const int32_t *pix_sorted, const int64_t *order, const int64_t *ts_sorted, const int32_t *seg,
+                      const uint8_t *hot, int64_t N, int32_t H, int32_t W, int64_t dt, int32_t include_self, uint8_t *keep,
+                      void *stream);
+
 /* ---- mesh (csrc/ren_mesh.hip) ------------------------------------------------------------------------- *
  * Triangle mesh of the level set sigma = level of a regular lattice of densities, by marching tetrahedra.  Everything below is
  * fixed by the lattice, so the output is the same index for index on every run and can be restated on the CPU.

@@ -164,6 +164,7 @@ SIGNATURES = {
     "ren_event_frame_compare": (c_int, [P, P, P, c_int32, c_int32, c_int32, c_double, c_double, P, P, P]),
     "ren_event_intervals": (c_int, [P, P, P, c_int64, P, P, P, P]),
     "ren_event_table_write": (c_int, [P, P, P, c_int32, P, P, P, c_int64, c_int64, P, c_int32, c_int32, P, P, P, P, P, P, P, P]),
+    "ren_event_support": (c_int, [P, P, P, P, P, c_int64, c_int32, c_int32, c_int64, c_int32, P, P]),
     "ren_mesh_classify": (c_int, [P, c_int32, c_int32, c_int32, c_float, P, P, P, P]),
     "ren_mesh_write": (c_int, [P, P, P, P, c_int32, c_int32, c_int32, c_float, POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                c_int64, c_int64, P, P, P]),

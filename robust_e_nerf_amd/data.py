@@ -209,13 +209,9 @@ def _bayer_channels(bayer_pattern: str):
     return [COLOR_CHANNEL[c] for c in bayer_pattern]
 
 
-def build_event_table(position, timestamp, polarity, calib, device):
-    """The raw stream of `raw_events.npz` -> (table, tau_max) with the table on `device`: what
-    `undistort_events(colorize_events(queue_raw_events(...)))` and `max_refractory_period` give, value for value, from one
-    stable sort by pixel and two launches (ops.event_intervals, ops.event_table_write; DESIGN 3.9).  The columns are uploaded
-    at their stored width; nothing but the number of kept events and the minimum interval comes back to the host.
-    Lengths and 0 <= x < img_width, 0 <= y < img_height are checked HERE, on the host arrays, before anything is uploaded:
-    that is what keeps the lookup-table gather in bounds.  tau_max: 0-dim float64, inf when no event is kept."""
+def _checked_raw_stream(position, timestamp, polarity, calib):
+    """The host checks of a raw stream against its calibration, before anything is uploaded: lengths, integer dtypes,
+    0 <= x < img_width, 0 <= y < img_height.  -> (position, timestamp, polarity as arrays, N, W, H)"""
     from . import ops
     position, timestamp, polarity = np.asarray(position), np.asarray(timestamp), np.asarray(polarity)
     n = len(timestamp)
@@ -233,6 +229,26 @@ def build_event_table(position, timestamp, polarity, calib, device):
         if int(lo[0]) < 0 or int(lo[1]) < 0 or int(hi[0]) >= W or int(hi[1]) >= H:
             raise ValueError(f"event positions span x {int(lo[0])} .. {int(hi[0])}, y {int(lo[1])} .. {int(hi[1])}: outside the "
                              f"{W} x {H} sensor of the calibration")
+    return position, timestamp, polarity, n, W, H
+
+
+def _pixel_keys(pos: torch.Tensor, W: int) -> torch.Tensor:
+    """int32 keys y * W + x of device positions (N, 2) uint16 / int32 / int64"""
+    if pos.dtype == torch.uint16:                                                 # one word x | y << 16 per event
+        word = pos.view(torch.int32).view(-1)
+        return ((word >> 16) & 0xffff) * W + (word & 0xffff)
+    return (pos[:, 1] * W + pos[:, 0]).to(torch.int32)
+
+
+def build_event_table(position, timestamp, polarity, calib, device):
+    """The raw stream of `raw_events.npz` -> (table, tau_max) with the table on `device`: what
+    `undistort_events(colorize_events(queue_raw_events(...)))` and `max_refractory_period` give, value for value, from one
+    stable sort by pixel and two launches (ops.event_intervals, ops.event_table_write; DESIGN 3.9).  The columns are uploaded
+    at their stored width; nothing but the number of kept events and the minimum interval comes back to the host.
+    Lengths and 0 <= x < img_width, 0 <= y < img_height are checked HERE, on the host arrays, before anything is uploaded:
+    that is what keeps the lookup-table gather in bounds.  tau_max: 0-dim float64, inf when no event is kept."""
+    from . import ops
+    position, timestamp, polarity, n, W, H = _checked_raw_stream(position, timestamp, polarity, calib)
     if polarity.dtype not in (np.bool_, np.uint8):
         if n and (int(polarity.min()) < 0 or int(polarity.max()) > 255):
             raise ValueError("polarity must fit one byte")
@@ -249,13 +265,7 @@ def build_event_table(position, timestamp, polarity, calib, device):
         empty = torch.empty(0, device=device, dtype=torch.int32)
         table = ops.event_table_write(empty.to(torch.uint8), empty, pos, ts, ts, pol, 0, H, W, lut_d, channels)
         return table, torch.tensor(float("inf"), dtype=torch.float64)
-    if pos.dtype == torch.uint16:                                                 # one word x | y << 16 per event
-        word = pos.view(torch.int32).view(-1)
-        pix = ((word >> 16) & 0xffff) * W + (word & 0xffff)
-    else:
-        pix = (pos[:, 1] * W + pos[:, 0]).to(torch.int32)
-    pix_sorted, order = torch.sort(pix, stable=True)
-    del pix
+    pix_sorted, order = torch.sort(_pixel_keys(pos, W), stable=True)
     valid, start_ts, min_diff = ops.event_intervals(pix_sorted, order, ts)
     del pix_sorted, order
     offsets = torch.cumsum(valid, 0, dtype=torch.int32)
@@ -265,15 +275,94 @@ def build_event_table(position, timestamp, polarity, calib, device):
     return table, torch.tensor(float(tau) if m else float("inf"), dtype=torch.float64)
 
 
-def load_event_table(root: str, permutation_seed: Optional[int] = None, use_cache: bool = True, device="cuda"):
+# ------------------------------------------------------------------------------------------- noise filter, on the device
+def hot_pixel_threshold(sum_c: int, sum_c2: int, n_active: int, k: float) -> int:
+    """T = floor(mu + k sigma) over the per-pixel event counts c_p of the pixels with c_p > 0, from their exact integer sums:
+    mu = sum c / |A|, sigma = sqrt(max(sum c^2 / |A| - mu^2, 0)), both float64.  A pixel is hot iff c_p > T.  The ONLY place
+    this formula lives (the filter's test reference calls it too).  No active pixel: 0."""
+    sum_c, sum_c2, n_active, k = int(sum_c), int(sum_c2), int(n_active), float(k)
+    if not (k >= 0.0 and math.isfinite(k)):
+        raise ValueError(f"the hot-pixel factor must be a finite number >= 0; got {k}")
+    if n_active < 1:
+        return 0
+    mu = sum_c / n_active
+    sigma = math.sqrt(max(sum_c2 / n_active - mu * mu, 0.0))
+    return int(math.floor(mu + k * sigma))
+
+
+def filter_events(position, timestamp, polarity, calib, dt=None, hot_sigma=None, include_self=False, device="cuda"):
+    """Which events of a raw stream are scene signal -> (keep: bool (N,) in stream order, stats: dict).  DESIGN 3.13:
+    a pixel is HOT when it holds more than `hot_pixel_threshold(...)` = floor(mu + hot_sigma sigma) events (mu, sigma over the
+    pixels with events; `hot_sigma=None`: none is hot); an event is SUPPORTED when another event at one of the eight
+    neighbouring in-sensor, non-hot pixels (at its own pixel too with `include_self`) lies 0 .. dt before it, ties included
+    (`dt` in the timestamps' unit; `dt=None`: all are); keep = not at a hot pixel and supported.  Polarity plays no part.
+    The host checks of `build_event_table` and "timestamps never decrease" come first, on the host arrays; then the table
+    build's key and stable sort, the segment starts and counts of the pixels, one host read of the three integer sums, and
+    ONE launch (ops.event_support).  N = 0 and both options None launch nothing.
+    stats: events, kept, dropped_unsupported, dropped_hot (every event at a hot pixel, supported or not), hot_pixels,
+    hot_threshold (None without hot_sigma), active_pixels."""
+    from . import ops
+    position, timestamp, polarity, n, W, H = _checked_raw_stream(position, timestamp, polarity, calib)
+    if dt is not None:
+        if isinstance(dt, (bool, float)) or not isinstance(dt, (int, np.integer)) or not 0 <= int(dt) <= ops.INT64_MAX:
+            raise ValueError(f"dt must be an integer in [0, 2^63) or None; got {dt!r}")
+        dt = int(dt)
+    if hot_sigma is not None:
+        hot_sigma = float(hot_sigma)
+        no_events = hot_pixel_threshold(0, 0, 0, hot_sigma)                       # refuses a factor that is negative or not finite
+    timestamp = timestamp.astype(np.int64, copy=False)
+    if n > 1 and bool((timestamp[1:] < timestamp[:-1]).any()):
+        at = int(np.argmax(timestamp[1:] < timestamp[:-1])) + 1
+        raise ValueError(f"timestamps must not decrease along the stream; event {at} is at {int(timestamp[at])} after "
+                         f"{int(timestamp[at - 1])}")
+    stats = dict(events=n, kept=n, dropped_unsupported=0, dropped_hot=0, hot_pixels=0,
+                 hot_threshold=None if hot_sigma is None else no_events, active_pixels=0)
+    if n == 0 or (dt is None and hot_sigma is None):
+        if n:
+            stats["active_pixels"] = len(np.unique(position[:, 1].astype(np.int64) * W + position[:, 0]))
+        return np.ones(n, bool), stats
+    if position.dtype not in (np.uint16, np.int32, np.int64):                    # in range: fits int32
+        position = position.astype(np.int32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    pix_sorted, order = torch.sort(_pixel_keys(up(position), W), stable=True)
+    seg = torch.searchsorted(pix_sorted, torch.arange(H * W + 1, device=device, dtype=torch.int32), out_int32=True)
+    counts = (seg[1:] - seg[:-1]).to(torch.int64)
+    active = counts > 0
+    sum_c, sum_c2, n_active = (int(v) for v in torch.stack([counts.sum(), (counts * counts).sum(), active.sum()]).cpu())
+    hot = None
+    if hot_sigma is not None:
+        stats["hot_threshold"] = hot_pixel_threshold(sum_c, sum_c2, n_active, hot_sigma)
+        hot = (counts > stats["hot_threshold"]).to(torch.uint8)
+    keep = ops.event_support(pix_sorted, order, up(timestamp)[order], seg, hot, H, W, dt, include_self)
+    tail = [keep.sum(dtype=torch.int64)]
+    if hot is not None:
+        tail += [hot.sum(dtype=torch.int64), (counts * hot).sum()]
+    tail = [int(v) for v in torch.stack(tail).cpu()]
+    stats.update(kept=tail[0], active_pixels=n_active)
+    if hot is not None:
+        stats.update(hot_pixels=tail[1], dropped_hot=tail[2])
+    stats["dropped_unsupported"] = n - stats["kept"] - stats["dropped_hot"]
+    return keep.cpu().numpy().astype(bool), stats
+
+
+def load_event_table(root: str, permutation_seed: Optional[int] = None, use_cache: bool = True, device="cuda",
+                     event_filter: Optional[dict] = None):
     """`load_events` + `load_max_refractory_period` in one pass -> (event table on `device`, tau_max).  With `use_cache` and
     both `events.pt` and `max_refractory_period.pt` present they are read and neither the raw file nor the library is
     touched; otherwise the table is built on the device (`build_event_table`) and, with `use_cache`, both caches are
     written in the forms `load_events` / `load_max_refractory_period` read (a cache file that exists is used as it is and
-    not replaced).  The permutation is `load_events`' own, applied as a gather on the device."""
+    not replaced).  The permutation is `load_events`' own, applied as a gather on the device.
+    event_filter: dict of `filter_events`' options (dt, hot_sigma, include_self): the raw stream is filtered first and the
+    table built from the kept events; neither cache is read or written (a cached table says nothing of how it was filtered)."""
     cache, tau_path = os.path.join(root, TF_EVENTS), os.path.join(root, MAX_REFRACTORY_PERIOD)
     have_events, have_tau = (use_cache and os.path.isfile(p) for p in (cache, tau_path))
-    if have_events and have_tau:
+    if event_filter is not None:
+        calib = np.load(os.path.join(root, CAMERA_CALIBRATION))
+        raw = np.load(os.path.join(root, RAW_EVENTS))
+        position, timestamp, polarity = raw["position"], raw["timestamp"], raw["polarity"]
+        keep, _ = filter_events(position, timestamp, polarity, calib, device=device, **event_filter)
+        events, tau_max = build_event_table(position[keep], timestamp[keep], polarity[keep], calib, device)
+    elif have_events and have_tau:
         events, tau_max = dict(torch.load(cache)), torch.load(tau_path)
     else:
         calib = np.load(os.path.join(root, CAMERA_CALIBRATION))

@@ -814,6 +814,44 @@ def event_table_write(valid: torch.Tensor, offsets: torch.Tensor, position: torc
     return out
 
 
+# ------------------------------------------------------------------------------- event filter
+EVENT_FILTER_THREADS = 256           # REN_EVENT_FILTER_THREADS: workgroup size
+EVENT_FILTER_MAX_BLOCKS = 2048       # REN_EVENT_FILTER_MAX_BLOCKS: more slots than their product take a second trip of the loop
+
+
+def event_support(pix_sorted: torch.Tensor, order: torch.Tensor, ts_sorted: torch.Tensor, seg: torch.Tensor,
+                  hot: Optional[torch.Tensor], height: int, width: int, dt: Optional[int], include_self: bool = False):
+    """keep (N,) uint8 in STREAM order: 1 where the event's pixel is not hot and another event at one of its eight in-sensor,
+    non-hot neighbour pixels (its own pixel too with `include_self`) lies 0 .. dt before it (include/ren_amd.h "event filter").
+    pix_sorted (N,) int32 keys y * width + x and order (N,) int64 as `torch.sort(stable=True)` returns them, ts_sorted (N,) int64
+    = timestamp[order] of a time-ordered stream, seg (height * width + 1,) int32 segment starts of the pixels in the sorted
+    stream, hot (height * width,) uint8 or None (no pixel is hot), dt >= 0 or None (every event is supported)."""
+    n = ts_sorted.shape[0]
+    height, width = int(height), int(width)
+    if pix_sorted.shape != (n,) or order.shape != (n,) or ts_sorted.dim() != 1:
+        raise ValueError(f"event_support: pix_sorted / order / ts_sorted must be ({n},); got {tuple(pix_sorted.shape)}, "
+                         f"{tuple(order.shape)}, {tuple(ts_sorted.shape)}")
+    if height < 1 or width < 1 or height * width > EVENT_TABLE_MAX_N or n > EVENT_TABLE_MAX_N:
+        raise ValueError(f"event_support: {n} events on {width} x {height} pixels: a sensor of at least one pixel, both counts below 2^31")
+    if seg.shape != (height * width + 1,):
+        raise ValueError(f"event_support: seg must be ({height * width + 1},); got {tuple(seg.shape)}")
+    if hot is not None and hot.shape != (height * width,):
+        raise ValueError(f"event_support: hot must be ({height * width},); got {tuple(hot.shape)}")
+    want = ((pix_sorted, torch.int32), (order, torch.int64), (ts_sorted, torch.int64), (seg, torch.int32), (hot, torch.uint8))
+    for name, (t, dtype) in zip(("pix_sorted", "order", "ts_sorted", "seg", "hot"), want):
+        if t is not None and (t.dtype != dtype or t.device != ts_sorted.device):
+            raise ValueError(f"event_support: {name} must be {dtype} on {ts_sorted.device}; got {t.dtype} on {t.device}")
+    if dt is not None and not 0 <= int(dt) <= INT64_MAX:
+        raise ValueError(f"event_support: dt must be in [0, 2^63) or None; got {dt}")
+    keep = torch.empty(n, device=ts_sorted.device, dtype=torch.uint8)
+    if n == 0:
+        return keep
+    check(_lib.load().ren_event_support(_ptr(pix_sorted), _ptr(order), _ptr(ts_sorted), _ptr(seg), _ptr(hot), n, height, width,
+                                        -1 if dt is None else int(dt), int(bool(include_self)), _ptr(keep), _stream()),
+          "ren_event_support")
+    return keep
+
+
 # ------------------------------------------------------------------------------- mesh (level set of a density lattice)
 MESH_MAX_POINTS = 2 ** 30            # include/ren_amd.h REN_MESH_MAX_POINTS
 MESH_MAX_VERTS = 2 ** 31             # the vertex total must stay below it: faces are int32

@@ -45,6 +45,12 @@ def main():
                          "(1 = the reference's exact int(budget / mean samples per ray), the default)")
     ap.add_argument("--no-validation", action="store_true", help="skip the validation epochs over views/transforms_val.json")
     ap.add_argument("--limit-val-batches", type=int, help="validate on the first N views only")
+    ap.add_argument("--event-support-us", type=float,
+                    help="noise filter before the table is built (data.filter_events): drop an event without another event at one "
+                         "of its eight neighbouring pixels in the D microseconds up to it (off by default)")
+    ap.add_argument("--hot-pixel-sigma", type=float,
+                    help="noise filter: drop the events of pixels that hold more than mean + K standard deviations of the "
+                         "per-pixel event count, and do not let them support their neighbours (off by default)")
     args = ap.parse_args()
     cfg = yaml.safe_load(open(args.config))
     rank, local_rank, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
@@ -72,7 +78,11 @@ def main():
     else:
         root = args.dataset_dir or dcfg["dataset_directory"]
         # the event table is built (or read from its caches) on the device together with tau_max: one sort, two launches
-        events, tau_max = data.load_event_table(root, dcfg.get("train_dataset_perm_seed"), device=dev)
+        event_filter = None
+        if args.event_support_us is not None or args.hot_pixel_sigma is not None:         # timestamps are nanoseconds
+            event_filter = dict(dt=None if args.event_support_us is None else int(round(args.event_support_us * 1e3)),
+                                hot_sigma=args.hot_pixel_sigma)
+        events, tau_max = data.load_event_table(root, dcfg.get("train_dataset_perm_seed"), device=dev, event_filter=event_filter)
         tau_max = tau_max.to(torch.float64)
         tab_ts, tab_pos, tab_quat = data.load_camera_poses(root)
         calib = data.load_calibration(root)

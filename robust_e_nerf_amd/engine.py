@@ -7,8 +7,9 @@ This is the "one level up" seam of SURVEY.md 8b: ``Renderer.forward`` replaces
 (robust_e_nerf/models/robust_e_nerf.py:301-517, 782-813) for the log-intensity-difference loss.
 Gradients are written straight into one flat buffer ([hash table | MLPs]) so the data-parallel
 all-reduce is a single RCCL call and Adam a single fused pass.
-Three concerns of the step live in objects of their own: the captured step (step_graph.StepGraphs), the side-stream fronts
-(fronts.StepFronts) and the device-side sample counts (sample_counts.SampleCounts, Renderer.counts).
+Five concerns of the step live in objects of their own: the captured step (step_graph.StepGraphs), the side-stream fronts
+(fronts.StepFronts), the device-side sample counts (sample_counts.SampleCounts, Renderer.counts), the event-generation parameters
+(event_params.EventParams, Trainer.events) and the optimiser's state and launches (optimizer.StepOptimizer, Trainer.opt).
 """
 from __future__ import annotations
 
@@ -22,7 +23,9 @@ import threading
 import torch
 
 from . import ops
+from .event_params import EventParams
 from .fronts import DiffFront, GradFront, StepFronts
+from .optimizer import StepOptimizer
 from .sample_counts import CountLog, SampleCounts, device_words
 from .step_graph import StepGraphs
 
@@ -846,29 +849,7 @@ class Trainer:
         self.tab_ts = tab_ts.to(dev).contiguous()
         self.tab_pos = tab_pos.to(dev, torch.float32).contiguous()
         self.tab_quat = tab_quat.to(dev, torch.float32).contiguous()
-        # Event-generation parameters (event_generation_params.py:51-84,162-203): evaluated here on the host as the reference
-        # does in float32 / float64, then DEVICE-RESIDENT (self.ep, ops.EP_*): every kernel takes C_p, C_n, tau and the 1 / C^k
-        # param weight from that block, and a trainable ratio / refractory period is stepped and re-evaluated on the device
-        # (ren_tau_adam_step, ren_event_params_refresh), so no launch of the next step waits for a host read of a parameter.
-        # The host-side attributes (c_p, mean_c, tau, ct_raw, tau_raw) are read back on demand.
-        ratio = torch.nn.functional.softplus(p2n_raw.detach().cpu().to(torch.float32))   # event_generation_params.py:51-70
-        neg = neg_ct.detach().cpu().to(torch.float32)
-        c_p, self.c_n = float(ratio * neg), float(neg)
-        mean_c = float((ratio * neg + neg) / 2)
-        traw, tmax = tau_raw.detach().cpu().to(torch.float64), tau_max.detach().cpu()
-        lim = torch.tensor(1e-4, dtype=torch.float64).logit().abs()
-        traw = tmax * (traw / tmax).clamp(-lim, lim)                          # :170-185
-        tau = float(tmax * torch.sigmoid(traw / tmax))                        # modules.py:58-74 (float64)
-        self.tau_max = tmax.to(torch.float64)
-        self._tau_shape = tuple(traw.shape)
-        ct_raw = float(p2n_raw.detach().reshape(-1)[0].to(torch.float32))
-        self._ep_host = [c_p, self.c_n, ct_raw, tau, 1.0 / mean_c, 1.0 / mean_c ** 2, float(traw.reshape(-1)[0]), 0.0]
-        self._ep_stale = False
-        self.ep = torch.tensor(self._ep_host, dtype=torch.float64, device=dev)
-        # trainable refractory period: a float64 scalar (event_generation_params.py:162-164); its gradient is assembled from
-        # per-ray forward-mode tangents dI/dt, its Adam group (state: exp_avg, exp_avg_sq) lives on the device as well
-        self._tau_raw_dev = traw.reshape(1).clone().to(dev)
-        self._tau_adam, self._tau_adam_steps = torch.zeros(2, dtype=torch.float64, device=dev), 0
+        self.events = EventParams(p2n_raw, neg_ct, tau_raw, tau_max, dev)    # C_p, C_n, tau: device block, host mirror, raw forms
         # small-parameter block: [bkgd_raw (C) | pad] with its own Adam state (group "others", lr default)
         self.small = torch.zeros(4, device=dev, dtype=torch.float32)
         self.small[: renderer.field.C] = bkgd_raw.to(dev, torch.float32).reshape(-1)
@@ -877,12 +858,9 @@ class Trainer:
         # background-only loss terms to these three; to the table / MLP gradients it adds exactly nothing)
         self._gs = torch.zeros(8, dtype=torch.float64, device=dev)
         self.small_grad = self._gs[0:2].view(torch.float32)
-        f = renderer.field
-        self.m = torch.zeros_like(f.flat)
-        self.v = torch.zeros_like(f.flat)
-        self.sm = torch.zeros_like(self.small)
-        self.sv = torch.zeros_like(self.small)
-        self.step_count = 0
+        self.ct_grad = self._gs[2:4].view(torch.float32)
+        self._tau_grad_dev = self._gs[4:5]                       # d loss / d tau (from per-ray forward-mode tangents dI/dt), on the device
+        self.opt = StepOptimizer(renderer.field.flat, self.small, self.events.ct)   # moments, step numbers, lr factor, launches
         self.world_size = world_size
         self.pg = process_group
         self.sync = None
@@ -902,46 +880,27 @@ class Trainer:
             self._device_counts = False
         self._update_dp_early()
         self.keep_ctx = False                                    # tests: aux["ctx"] = the render's context (rays, samples, features)
-        # optimiser state on the device (ABI 25, ops.HY_*): Adam step numbers and bias corrections, and the sticky skip word a
-        # captured step raises when one of its device-side counts did not fit (step_graph.StepGraphs)
-        self._hyper = torch.zeros(8, dtype=torch.float64, device=dev)
         # Trainer.step: None = auto (a step shape seen three times in a row), False = never (REN_STEP_GRAPH=0|off)
         self.use_graph: Optional[bool] = False if os.environ.get("REN_STEP_GRAPH", "") in ("0", "off") else None
         self.step_graphs = StepGraphs()
         self.graph_replays = self.graph_captures = 0
-        self.lr_scale = 1.0
-        # trainable C_p / C_n ratio (softplus-parametrised scalar, its own Adam group with lr 0.1:
-        # robust_e_nerf.py:800-803).  Its loss dependence is through the per-event targets and the 1/C^k
-        # normalisation only, i.e. O(B) elementwise work on already rendered predictions.
-        self.ct = torch.zeros(4, device=dev, dtype=torch.float32)
-        self.ct[0] = p2n_raw.detach().reshape(-1)[0].to(dev, torch.float32)
-        self.ct_grad, self.ct_m, self.ct_v = self._gs[2:4].view(torch.float32), torch.zeros_like(self.ct), torch.zeros_like(self.ct)
-        self._tau_grad_dev = self._gs[4:5]                       # d loss / d tau, accumulated on the device
 
-    # ---- host views of the device-resident event parameters (a read-back when they have moved since the last look) ----
-    def _ep(self):
-        if self._ep_stale:
-            self._ep_host, self._ep_stale = self.ep.tolist(), False
-        return self._ep_host
-
-    c_p = property(lambda self: self._ep()[ops.EP_CP])
-    mean_c = property(lambda self: (self._ep()[ops.EP_CP] + self._ep()[ops.EP_CN]) / 2)
-    tau = property(lambda self: self._ep()[ops.EP_TAU])
-    ct_raw = property(lambda self: self._ep()[ops.EP_RAW])
-
-    @property
-    def tau_raw(self) -> torch.Tensor:
-        """the raw refractory period (float64, host copy, shaped like the constructor's tau_raw)"""
-        return self._tau_raw_dev.cpu().reshape(self._tau_shape)
-
-    def _refresh_event_params(self):
-        ops.event_params_refresh(self.ct, self.c_n, self._tau_raw_dev, float(self.tau_max), self.ep)
-        self._ep_stale = True
-
-    def _pw_dev(self, kind):
-        """device scalar of the param weight 1 / C^k (loss.param_weight.*, robust_e_nerf.py:470-486), None for k = 0"""
-        return {None: None, "mean_contrast_reciprocal": self.ep[ops.EP_INV_C: ops.EP_INV_C + 1],
-                "mean_contrast_reciprocal_sq": self.ep[ops.EP_INV_C2: ops.EP_INV_C2 + 1]}[kind]
+    # ---- read-throughs to self.events / self.opt: the names that scripts, checkpoints and the benchmark use ----
+    ct = property(lambda self: self.events.ct)
+    _tau_raw_dev = property(lambda self: self.events.tau_raw_dev)
+    tau = property(lambda self: self.events.tau)
+    tau_raw = property(lambda self: self.events.tau_raw)
+    tau_max = property(lambda self: self.events.tau_max)
+    c_p = property(lambda self: self.events.c_p)
+    c_n = property(lambda self: self.events.c_n)
+    mean_c = property(lambda self: self.events.mean_c)
+    ct_raw = property(lambda self: self.events.ct_raw)
+    load_event_params = property(lambda self: self.events.load)
+    step_count = property(lambda self: self.opt.step_count)
+    lr_scale = property(lambda self: self.opt.lr_scale, lambda self, v: setattr(self.opt, "lr_scale", v))
+    set_epoch = property(lambda self: self.opt.set_epoch)
+    optimizer_state_dict = property(lambda self: self.opt.state_dict)
+    load_optimizer_state_dict = property(lambda self: self.opt.load_state_dict)
 
     def device_counts_ok(self) -> bool:
         """Renders of this trainer keep their sample counts on the device (what Renderer.device_counts_ok asks for).  A
@@ -978,12 +937,19 @@ class Trainer:
         return self._tau_grad_dev.cpu().reshape(())
 
     # ---- Bayer sensor: every event sees one colour channel of the (., 3) render (`bayering`, robust_e_nerf.py:887-890)
-    def _channel_index(self, batch, repeat: int):
+    def _channels(self, batch):
+        """the events' colour channels as the batch has them (None: monochrome sensor)"""
         if self.r.field.C == 1:
             return None
         if "channel_idx" not in batch:
             raise ValueError("radiance_dim 3 (Bayer sensor) needs batch['channel_idx'] (data.colorize_events)")
-        ch = batch["channel_idx"].to(torch.int64)
+        return batch["channel_idx"]
+
+    def _channel_index(self, batch, repeat: int):
+        ch = self._channels(batch)
+        if ch is None:
+            return None
+        ch = ch.to(torch.int64)
         return (torch.cat([ch] * repeat) if repeat > 1 else ch)[:, None]
 
     @staticmethod
@@ -1006,19 +972,19 @@ class Trainer:
         err, w, pwk = (t.err_diff, t.w_diff, t.pw_diff) if kind == "diff" else (t.err_grad, t.w_grad, t.pw_grad)
         ops.event_param_grad(kind, err, pwk, pred.contiguous(), valid, batch, 0.0, 0.0, 0.0, 0.0, w,
                              ct_grad=self.ct_grad if t.train_contrast_threshold else None,
-                             tau_grad=self._tau_grad_dev if t.train_refractory_period else None, ep=self.ep)
+                             tau_grad=self._tau_grad_dev if t.train_refractory_period else None, ep=self.events.ep)
 
     # ---- a2-a4: event correction + supervision timestamps: one launch (ren_event_prepare) ---------------------
     def _prepare(self, batch):
         B = batch["position"].shape[0]
-        p = ops.event_prepare(batch, 0.0, 0.0, 0.0, ep=self.ep)
+        p = ops.event_prepare(batch, 0.0, 0.0, 0.0, ep=self.events.ep)
         return p["ts"][:B], p["ts"][B:], p["target_diff"]
 
     # ---- the parameter-independent front of the l_diff step, and its prefetch ------------------------------------------
     def _front(self, batch, jitter_start, jitter_end) -> DiffFront:
         """event correction -> supervision timestamps -> poses -> rays of the start and end renders (a2-a6)"""
         t = self.t
-        prep = ops.event_prepare(batch, 0.0, 0.0, 0.0, with_dtau=t.train_refractory_period, ep=self.ep)
+        prep = ops.event_prepare(batch, 0.0, 0.0, 0.0, with_dtau=t.train_refractory_period, ep=self.events.ep)
         jitter = None
         if jitter_start is not None:
             # jitter_end None: jitter_start already holds the 2B uniforms of both renders (start rays first)
@@ -1075,13 +1041,11 @@ class Trainer:
             colors, opac, depth, ctx = r.forward(front.o, front.d, jitter, bkgd, training=True, save=True, begun=begun,
                                                  device_counts=dc)
         # a16 + a18: intensity epilogue, validity, Bayer channel, loss and its gradient: two launches (ren_event_diff_loss_*)
-        if f.C > 1 and "channel_idx" not in batch:
-            raise ValueError("radiance_dim 3 (Bayer sensor) needs batch['channel_idx'] (data.colorize_events)")
-        chan = batch["channel_idx"].to(torch.uint8).contiguous() if f.C > 1 else None
+        chan = self._channels(batch).to(torch.uint8).contiguous() if f.C > 1 else None
         need_param = t.train_contrast_threshold or t.train_refractory_period
         # loss weight x 1 / C^k (robust_e_nerf.py:470-486); the latter from the device block
         L = ops.event_diff_loss(colors, opac, chan, target, t.err_diff, t.w_diff, r.cfg.min_modeled_intensity,
-                                use_validity=not t.bkgd_is_param, want_pred=need_param, scale_dev=self._pw_dev(t.pw_diff))
+                                use_validity=not t.bkgd_is_param, want_pred=need_param, scale_dev=self.events.pw(t.pw_diff))
         loss, g_colors, inten = L["loss"], L["g_colors"], L["intensity"]
         i_s, i_e = inten[:B], inten[B:]
         if need_param:
@@ -1135,7 +1099,7 @@ class Trainer:
         the last three (the "merged" placement marches these rays together with the l_diff render's)"""
         from . import jvp
         t = self.t
-        prep = ops.event_prepare(batch, 0.0, 0.0, 0.0, with_grad_ts=True, with_dtau=t.train_refractory_period, ep=self.ep)
+        prep = ops.event_prepare(batch, 0.0, 0.0, 0.0, with_grad_ts=True, with_dtau=t.train_refractory_period, ep=self.events.ep)
         ts_g = prep["ts_grad"]
         ddd = None
         if t.train_refractory_period:                                  # tau moves ts_g: second-order tangent
@@ -1189,7 +1153,7 @@ class Trainer:
                                                        want_valid=not t.bkgd_is_param)
         loss_sum = jvp.grad_loss_fwd(inten, intend, target, valid, t.err_grad)
         g_i, g_id, loss = jvp.grad_loss_bwd(inten, intend, target, valid, t.err_grad, t.w_grad, loss_sum,
-                                            scale_dev=self._pw_dev(t.pw_grad), want_loss=True)
+                                            scale_dev=self.events.pw(t.pw_grad), want_loss=True)
         if t.train_contrast_threshold or t.train_refractory_period:
             self._param_grad(batch, dlog, "grad", valid)
         if t.train_refractory_period:
@@ -1231,72 +1195,9 @@ class Trainer:
             self._mean_s_dev = aux[P_.AUX_MEAN_S].clone()
             aux.zero_()
             self.last_collectives = self.sync.reset_count()
-        self.step_count += 1
-        gs = 1.0 / (self.world_size * accumulate_grad_batches)            # mean over ranks and accumulated micro-batches
-        lr = self.t.lr * self.lr_scale
-        # step numbers / bias corrections live on the device (ops.HY_*): the same launches serve the eager step and a captured
-        # one, whose renders' overflow words raise the skip word instead (step_graph.StepGraphs)
-        hy = self._hyper
-        if self.t.train_refractory_period:
-            self._tau_adam_steps += 1
         stats = [log.stats for log, _ in self.r._capture.passes] if self.r._capture is not None else []
-        ops.step_tick(hy, self.t.betas, stats=stats, tick_tau=self.t.train_refractory_period)
-        ops.adam_step_dev(f.flat, f.grad, self.m, self.v, hy, lr=lr, betas=self.t.betas, eps=self.t.eps,
-                          weight_decay=self.t.weight_decay, grad_scale=gs, zero_grad=True)
-        if getattr(f, "n_wn_g", 0):
-            f.refresh()
-        ops.adam_step_dev(self.small, self.small_grad, self.sm, self.sv, hy, lr=lr, betas=self.t.betas, eps=self.t.eps,
-                          weight_decay=0.0, grad_scale=gs, zero_grad=True)
-        if self.t.train_refractory_period:
-            # float64 scalar, Adam group with lr = tau_max * relative lr (robust_e_nerf.py:804-807);
-            # tau = tau_max sigmoid(raw / tau_max)  =>  d tau / d raw = sigmoid'(raw / tau_max): one single-thread launch
-            ops.tau_adam_step_dev(self._tau_raw_dev, self._tau_grad_dev, self._tau_adam, float(self.tau_max), hy,
-                                  lr=float(self.tau_max) * self.t.relative_lr_refractory_period * self.lr_scale,
-                                  betas=self.t.betas, eps=self.t.eps, grad_scale=gs)
-        if self.t.train_contrast_threshold:
-            ops.adam_step_dev(self.ct, self.ct_grad, self.ct_m, self.ct_v, hy, lr=self.t.lr_contrast_threshold * self.lr_scale,
-                              betas=self.t.betas, eps=self.t.eps, weight_decay=0.0, grad_scale=gs, zero_grad=True)
-        if self.t.train_refractory_period or self.t.train_contrast_threshold:
-            self._refresh_event_params()                     # clamp (:170-185), C_p, tau, 1 / C^k for the next step's kernels
-
-    def _sync_hyper(self):
-        """device-side step numbers <- the host's (after loading a checkpoint, or a repeated step); clears the skip word"""
-        h = [0.0] * 8
-        h[ops.HY_STEP], h[ops.HY_TAU_STEP] = float(self.step_count), float(self._tau_adam_steps)
-        self._hyper.copy_(torch.tensor(h, dtype=torch.float64))
-
-    # ---- optimiser state for checkpoints (what ModelCheckpoint keeps under "optimizer_states": scripts/run.py:66-68) ----
-    def optimizer_state_dict(self) -> Dict[str, object]:
-        cpu = lambda t: t.detach().cpu().clone()
-        sd = dict(step_count=self.step_count, exp_avg=cpu(self.m), exp_avg_sq=cpu(self.v), small_exp_avg=cpu(self.sm),
-                  small_exp_avg_sq=cpu(self.sv), ct_exp_avg=cpu(self.ct_m), ct_exp_avg_sq=cpu(self.ct_v))
-        if self._tau_adam_steps:
-            m, v = self._tau_adam.tolist()
-            sd["tau_adam"] = dict(step=self._tau_adam_steps, exp_avg=m, exp_avg_sq=v)
-        return sd
-
-    def load_optimizer_state_dict(self, sd: Dict[str, object]):
-        self.step_count = int(sd["step_count"])
-        for dst, key in ((self.m, "exp_avg"), (self.v, "exp_avg_sq"), (self.sm, "small_exp_avg"),
-                         (self.sv, "small_exp_avg_sq"), (self.ct_m, "ct_exp_avg"), (self.ct_v, "ct_exp_avg_sq")):
-            dst.copy_(sd[key].to(dst.device, dst.dtype))
-        if "tau_adam" in sd:
-            ta = sd["tau_adam"]
-            if "state" in ta:                                # round <= 4 checkpoints: a torch.optim.Adam state dict
-                st = next(iter(ta["state"].values()), None)
-                ta = dict(step=int(st["step"]), exp_avg=float(st["exp_avg"]), exp_avg_sq=float(st["exp_avg_sq"])) if st else None
-            if ta:
-                self._tau_adam_steps = int(ta["step"])
-                self._tau_adam.copy_(torch.tensor([ta["exp_avg"], ta["exp_avg_sq"]], dtype=torch.float64))
-        self._sync_hyper()
-
-    def load_event_params(self, p2n_raw: Optional[torch.Tensor] = None, tau_raw: Optional[torch.Tensor] = None):
-        """restore the learned contrast-threshold ratio / refractory period (checkpoint resume)"""
-        if p2n_raw is not None:
-            self.ct[0] = p2n_raw.detach().reshape(-1)[0].to(self.ct.device, torch.float32)
-        if tau_raw is not None:
-            self._tau_raw_dev.copy_(tau_raw.detach().to(torch.float64).reshape(1))
-        self._refresh_event_params()
+        self.opt.apply((f, self.small, self.small_grad, self.ct_grad, self._tau_grad_dev), self.t, self.events,
+                       1.0 / (self.world_size * accumulate_grad_batches), stats)   # (mean over ranks and accumulated micro-batches)
 
     def update_train_batch_size(self, aux, eff_ray_sample_batch_size: int = 1 << 20, accumulate_grad_batches: int = 1,
                                 batch_index: int = 0) -> Optional[int]:
@@ -1325,10 +1226,6 @@ class Trainer:
         if aux.get("grad") is not None:
             means.append(aux["grad"]["n"] / max(aux["grad"]["rays"], 1))
         return means
-
-    def set_epoch(self, epoch: int, milestones=(20, 30, 36), gamma: float = 0.33):
-        """MultiStepLR stepped per epoch (robust_e_nerf.py:818-832, synthetic.yaml:113-128)."""
-        self.lr_scale = gamma ** sum(1 for m in milestones if epoch >= m)
 
     def step(self, batch, jitter_start=None, jitter_end=None, global_step: Optional[int] = None, jitter_grad=None,
              batch_index: Optional[int] = None, accumulate_grad_batches: int = 1):

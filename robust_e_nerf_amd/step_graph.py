@@ -119,19 +119,18 @@ class StepGraphs:
             log.arm()
         rec.graph.replay()
         tr.graph_replays += 1
-        tr._ep_stale = True
+        tr.events.mark_stale()
         if not tr.r.counts.settle(rec.passes):              # (the step's aux is the first pass's)
             if tr.world_size > 1:                    # (data parallelism: the graph ends where the gradient exchange begins)
                 tr._optimizer_after_passes(rec.aux)
             else:
-                tr.step_count += 1
-                tr._tau_adam_steps += int(tr.t.train_refractory_period)
+                tr.opt.advance_host(tr.t.train_refractory_period)
             return rec.loss, rec.aux
         # a count did not fit: the graph's optimiser launches saw the skip word and changed nothing; its passes' gradients go, and
         # the step runs again with host-side counts (data parallelism: by this rank alone, before the collective)
         tr._clear_grads()
         if tr.world_size == 1:
-            tr._sync_hyper()
+            tr.opt.sync_hyper()
         return tr.r.counts.repeat(tr, lambda: tr._step_passes(batch, jitter_start, jitter_end, jitter_grad))
 
     def _capture(self, tr, key, batch, jitter_start, jitter_grad) -> CapturedStep | None:
@@ -155,7 +154,7 @@ class StepGraphs:
         dump = os.environ.get("REN_STEP_GRAPH_DUMP")             # debugging: <prefix><capture number>.dot of every captured step
         if dump:
             g.enable_debug_mode()
-        host_state = (tr.step_count, tr._tau_adam_steps, tr._ep_stale)
+        host_state = tr.opt.host_state()
         r._capture = cap
         tr.fronts.reset()                            # (a front of the eager steps is not part of this one, nor this one's of theirs)
         try:
@@ -168,7 +167,7 @@ class StepGraphs:
         finally:
             r._capture = None
             tr.fronts.reset()
-            tr.step_count, tr._tau_adam_steps, tr._ep_stale = host_state       # (nothing ran)
+            tr.opt.restore_host_state(host_state)    # (nothing ran; tr.events may stay marked stale: the replay or eager step that follows marks it anyway)
         tr.graph_captures += 1
         if dump:
             g.debug_dump(f"{dump}{tr.graph_captures}.dot")
@@ -178,16 +177,16 @@ class StepGraphs:
         ev = self.eager_ev
         if tr.use_graph is None and ev is not None and ev[0] == key[1:]:
             t_eager, e0, e1 = ev[1].elapsed_time(ev[2]), torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            tr._hyper[ops.HY_SKIP: ops.HY_SKIP + 1].fill_(1.0)             # (the optimiser's skip word: parameters and moments stay)
+            tr.opt.raise_skip()                      # (the optimiser's skip word: parameters and moments stay)
             rec.graph.replay()                       # (first replay of a fresh executable: not timed)
             e0.record()
             for _ in range(3):
                 rec.graph.replay()
             e1.record()
             tr._clear_grads()
-            tr._sync_hyper()
+            tr.opt.sync_hyper()
             if tr.t.train_refractory_period or tr.t.train_contrast_threshold:
-                tr._refresh_event_params()
+                tr.events.refresh()
             torch.cuda.synchronize()
             rec.ms = (e0.elapsed_time(e1) / 3, t_eager)
             if rec.ms[0] > 0.97 * t_eager:

@@ -85,8 +85,8 @@ def _worker(rank, port, out_dir, backend="gloo", one_gpu_per_rank=False):
         sb, sj = _shard(b, jit, rank * B, (rank + 1) * B)
         tr.step(sb, sj[0], sj[1], global_step=0, jitter_grad=sj[2], batch_index=bi, accumulate_grad_batches=2)
     res["collectives"] = tr.last_collectives
-    res["m_accum"] = tr.m.clone()
-    res["ct_m"] = tr.ct_m.clone()
+    res["m_accum"] = tr.opt.m.clone()
+    res["ct_m"] = tr.opt.ct_m.clone()
     # ---- 2. a rank without samples (empty occupancy grid on rank 1 only) still matches its peer's collectives
     tr2, _ = mk(WORLD, w_grad=0.0)
     if rank == 1:
@@ -96,7 +96,7 @@ def _worker(rank, port, out_dir, backend="gloo", one_gpu_per_rank=False):
     loss, aux = tr2.step(sb, sj[0], sj[1])
     res["empty_n"] = aux["n"]
     res["empty_collectives"] = tr2.last_collectives
-    res["empty_m_nonzero"] = int((tr2.m != 0).sum())
+    res["empty_m_nonzero"] = int((tr2.opt.m != 0).sum())
     del tr2
     # ---- 3. K steps: occupancy refresh inside, dynamic batch size; replicas must stay identical
     tr3, _ = mk(WORLD)
@@ -110,7 +110,7 @@ def _worker(rank, port, out_dir, backend="gloo", one_gpu_per_rank=False):
         Bk = max(64, min(512, new))
     res["sizes"] = sizes
     torch.cuda.synchronize()
-    mine = [tr3.r.field.flat, tr3.m, tr3.v, tr3.small, tr3.ct, tr3.r.binary.float(), tr3.r.occs]
+    mine = [tr3.r.field.flat, tr3.opt.m, tr3.opt.v, tr3.small, tr3.ct, tr3.r.binary.float(), tr3.r.occs]
     same = []
     for t in mine:
         tc = t.detach().clone() if backend == "nccl" else t.detach().cpu()
@@ -192,13 +192,13 @@ def check_two_rank_results(got):
             sb, sj = _shard(b, jit, r * B, (r + 1) * B)
             tr.step(sb, sj[0], sj[1], global_step=0, jitter_grad=sj[2], batch_index=bi, accumulate_grad_batches=4)
             bi += 1
-    m_ref, m_dp = tr.m.cpu(), got["m_accum"]
+    m_ref, m_dp = tr.opt.m.cpu(), got["m_accum"]
     n_table = tr.r.field.n_table
     for name, sl in (("table", slice(0, n_table)), ("mlp", slice(n_table, tr.r.field.n_params))):
         err = float((m_dp[sl] - m_ref[sl]).abs().max() / m_ref[sl].abs().max())
         print(f"2 ranks x 2 micro-batches vs 1 rank x 4: first moment of the {name} gradient, max rel err {err:.2e}")
         assert err < 2e-5, (name, err)
-    assert float((got["ct_m"] - tr.ct_m.cpu()).abs().max()) <= 1e-5 * float(tr.ct_m.abs().max())
+    assert float((got["ct_m"] - tr.opt.ct_m.cpu()).abs().max()) <= 1e-5 * float(tr.opt.ct_m.abs().max())
     # with the sample counts on the device (the default for the occupancy sampler) no pass contains a collective: ONE
     # all-reduce of the packed buffer per optimiser step, at the settle point (engine.Trainer.device_counts_ok)
     assert got["collectives"] == 1, got["collectives"]

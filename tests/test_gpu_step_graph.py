@@ -57,7 +57,7 @@ def test_replayed_steps_repeat_the_eager_steps(amd, full_table_cache, w_grad, tr
     got, tr1 = _run(engine, g, table, True, steps=steps, w_grad=w_grad, trainable=trainable)
     assert tr0.graph_replays == 0 and tr1.graph_replays >= steps - 2, (tr1.graph_replays, tr1.graph_captures)
     assert tr1.device_count_overflows == 0 and tr1.step_count == tr0.step_count == steps
-    hy = tr1._hyper.tolist()
+    hy = tr1.opt.hyper.tolist()
     assert hy[ops.HY_STEP] == steps and hy[ops.HY_SKIP] == 0.0
     _same(got, ref, tol=2e-4 if trainable else 2e-5, ptol=1e-3)
 
@@ -76,7 +76,7 @@ def test_auto_mode_captures_a_shape_that_repeats(amd, full_table_cache):
     assert (len(kept) >= 1 and tr.graph_replays >= 1) or sum(tr._graph_bad.values()) >= 1
     for sg in kept:
         assert sg["ms"][0] <= 0.97 * sg["ms"][1]
-    hy = tr._hyper.tolist()
+    hy = tr.opt.hyper.tolist()
     assert hy[ops.HY_STEP] == 8 and hy[ops.HY_SKIP] == 0.0
     ref, _ = _run(engine, g, table, False, steps=8, w_grad=1e-3)
     _same(got, ref, ptol=1e-3)
@@ -91,7 +91,7 @@ def test_overflow_inside_a_replayed_step_is_repeated_exactly(amd, full_table_cac
     ref, _ = _run(engine, g, table, False, w_grad=1e-3)
     got, tr = _run(engine, g, table, True, w_grad=1e-3, squeeze_at=3)
     assert tr.device_count_overflows == 1 and tr.step_count == 6
-    hy = tr._hyper.tolist()
+    hy = tr.opt.hyper.tolist()
     assert hy[ops.HY_STEP] == 6 and hy[ops.HY_SKIP] == 0.0
     _same(got, ref, ptol=1e-3)
 
@@ -111,17 +111,17 @@ def test_replayed_passes_give_the_eager_passes_gradients(amd, full_table_cache, 
     f = tr.r.field
     grads = lambda: dict(grad_all=f.grad_all.clone(), small=tr.small_grad.clone(), ct=tr.ct_grad.clone(), tau=tr._tau_grad_dev.clone())
     tr._clear_grads()
-    params = (f.flat.clone(), tr.m.clone(), tr.v.clone(), tr.small.clone(), tr.ct.clone(), tr._tau_raw_dev.clone())
-    tr._hyper[ops.HY_SKIP: ops.HY_SKIP + 1].fill_(1.0)
+    params = (f.flat.clone(), tr.opt.m.clone(), tr.opt.v.clone(), tr.small.clone(), tr.ct.clone(), tr._tau_raw_dev.clone())
+    tr.opt.raise_skip()
     for log, _ in rec.passes:
         log.arm()
     rec.graph.replay()
     assert not any(log.overflowed for log, _ in rec.passes)
     torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(params, (f.flat, tr.m, tr.v, tr.small, tr.ct, tr._tau_raw_dev)))
+    assert all(torch.equal(a, b) for a, b in zip(params, (f.flat, tr.opt.m, tr.opt.v, tr.small, tr.ct, tr._tau_raw_dev)))
     got = grads()
     tr._clear_grads()
-    tr._sync_hyper()                                     # (clears the skip word)
+    tr.opt.sync_hyper()                                  # (clears the skip word)
     tr._step_passes(rec.batch, rec.j0, None, rec.j2, optimizer=False)
     torch.cuda.synchronize()
     assert tr.device_count_overflows == 0 and tr.graph_replays == replays

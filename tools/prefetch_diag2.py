@@ -55,7 +55,7 @@ def run(use):
                    steps=steps, tr=tr)
         tr.optimizer_step()
         rec["flat"] = tr.r.field.flat.clone()
-        rec["m"], rec["v"] = tr.m.clone(), tr.v.clone()
+        rec["m"], rec["v"] = tr.opt.m.clone(), tr.opt.v.clone()
         res.append(rec)
     torch.cuda.synchronize()
     return res

@@ -1011,8 +1011,41 @@ int ren_mesh_simplify_vertices(const uint64_t *sums, const uint32_t *count, cons
 int ren_mesh_simplify_compact_faces(const int32_t *ids, const int32_t *keep, const int64_t *foff, const int64_t *uoff, int64_t F,
                                     int64_t clusters, int64_t F_out, int32_t *faces, void *stream);
 
+/* ---- mesh distance (csrc/ren_mesh_distance.hip) -------------------------------------------------------- *
+ * Exact nearest neighbour of nq query points among nr reference points (both (n, 3) float32, counts below 2^31) through a
+ * uniform grid of cubic cells: what surface-to-surface distances (accuracy, completeness, Chamfer, F-score) are made of.
+ * Distance, float32, every operation rounded on its own: dx = q.x - p.x, dy, dz likewise; d2 = (dx*dx + dy*dy) + dz*dz.
+ * Result per query: the minimum of d2 over the references and, among references of equal d2, the smallest index.  Both are
+ * functions of the two point sets alone: they do not depend on lo, h or the grid, which only decide the work.
+ * Grid: cells of edge h (inv_h its float32 reciprocal, |h * inv_h - 1| <= 2^-16) from the corner lo (three finite floats on
+ * the HOST), g = (gx, gy, gz) cells, each extent in [1, REN_NN_MAX_EXTENT].  Cell of a point, per axis and in float32:
+ * fl = floor((x_a - lo_a) * inv_h); c_a = 0 if not fl >= 0 (NaN lands here), g_a - 1 if fl >= g_a, else int(fl): a point
+ * outside the box belongs to the nearest border cell.  Cell id (c_z * gy + c_y) * gx + c_x: x runs fastest.
+ * ren_nn_cells: cell[i] (int32) of pts (n, 3).  One launch, one point per lane; n == 0 launches nothing.
+ *   pts, n: the points; lo, inv_h, gx, gy, gz: the grid; cell: n int32 out.
+ * The caller groups the references by cell (a stable sort of the ids) and hands ren_nn_search
+ *   ref_records (nr, 4) float32, 16-byte aligned: row j = (x, y, z, the 32 bits of the ORIGINAL index as they stand) of the
+ *     reference at sorted position j;
+ *   cell_start (gx gy gz + 1) int32: the records of cell c are [cell_start[c], cell_start[c + 1]).
+ * ren_nn_search: d2[q] (float32) and idx[q] (int32, an original index) for queries (nq, 3).  One launch, one query per lane,
+ * in the caller's order (lanes whose queries share cells walk the same records: sort the queries by cell first).  From the
+ * query's own cell (clamped as above) the lane visits the cells at Chebyshev distance r = 0, 1, 2, ..., clipped to the grid;
+ * after shell r >= 1 it stops when best d2 < b * b with b = (float(r) - 2^-6) * h in float32, and after any shell when the
+ * visited block covers the grid.  No reference outside the visited block can then have a d2 below or equal to the best one
+ * (DESIGN 3.14), also for queries and references outside the box.  At most max(gx, gy, gz) shells; every range end read from
+ * cell_start is clamped into [0, nr] before a record is read.  nr == 0 gives d2 = +inf, idx = -1; nq == 0 launches nothing.
+ *   queries, nq; ref_records, cell_start, nr; lo, h, inv_h, gx, gy, gz: the grid the records were grouped on; d2, idx: nq out.
+ * REN_ERR_BAD_ARG before any launch for a negative count or one of 2^31 and beyond, a grid extent below 1 or above
+ * REN_NN_MAX_EXTENT, h or inv_h not positive and finite (h below FLT_MIN), h * inv_h further than 2^-16 from 1, lo null or
+ * not finite, a null pointer that a positive count needs, a pointer not aligned to its element (ref_records: 16 bytes). */
+#define REN_NN_MAX_EXTENT 512
+int ren_nn_cells(const float *pts, int64_t n, const float *lo, float inv_h, int32_t gx, int32_t gy, int32_t gz, int32_t *cell,
+                 void *stream);
+int ren_nn_search(const float *queries, int64_t nq, const float *ref_records, const int32_t *cell_start, int64_t nr,
+                  const float *lo, float h, float inv_h, int32_t gx, int32_t gy, int32_t gz, float *d2, int32_t *idx, void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
-/* out[c] = sum_r in[r*C + c]   (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
+/* out[c] = sum_r in[r*C + c]  (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);
 /* NeRF.render_bkgd as a softplus-parametrised parameter (models/nerf.py:81-88): bkgd[C] = softplus(raw[C]); and its gradient
  * from the per-ray d_bkgd of ren_composite_bwd: grad_raw[c] += sigmoid(raw[c]) * sum_r d_bkgd_per_ray[r, c] */

@@ -177,6 +177,8 @@ SIGNATURES = {
     "ren_mesh_simplify_vertices": (c_int, [P, P, P, P, P, c_int32, c_int32, c_int32, POINTER(c_double), POINTER(c_double), c_int64,
                                            c_int64, P, P]),
     "ren_mesh_simplify_compact_faces": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P]),
+    "ren_nn_cells": (c_int, [P, c_int64, POINTER(c_float), c_float, c_int32, c_int32, c_int32, P, P]),
+    "ren_nn_search": (c_int, [P, c_int64, P, P, c_int64, POINTER(c_float), c_float, c_float, c_int32, c_int32, c_int32, P, P, P]),
 }
 
 _lib = None

@@ -16,7 +16,9 @@ filled, with the components labelled on the GPU (`components`: ops.mesh_componen
 
 `simplify` (export's simplify=k) reduces the extracted mesh by vertex clustering: one vertex per occupied cell of a grid of k
 lattice spacings (`cluster_grid`), collapsed and repeated faces dropped (ops.mesh_simplify_*, include/ren_amd.h "mesh
-simplify").  The lattice resolution then sets the fidelity of the sampling and k the size of the file.
+simplify").  The lattice resolution then sets the fidelity of the sampling and k the size of the file; what k costs in geometry
+is measured on request (`simplification_error`, export's simplify_error=n: the scores of mesh_distance.compare between the
+simplified and the extracted mesh).
 """
 from __future__ import annotations
 
@@ -216,6 +218,31 @@ def simplify(verts: torch.Tensor, faces: torch.Tensor, lo: Sequence[float], hi: 
 
 _simplify = simplify                     # `export` has a parameter of the function's name
 
+
+def simplification_error(verts: torch.Tensor, faces: torch.Tensor, verts_0: torch.Tensor, faces_0: torch.Tensor,
+                         lo: Sequence[float], hi: Sequence[float], res: Res, samples: int, seed: int = 0) -> Optional[dict]:
+    """the simplified mesh (verts, faces) against the extracted one (verts_0, faces_0) it was made of, a lattice of `res` points
+    over [lo, hi]: mesh_distance.compare with the simplified mesh as A -- accuracy: simplified -> extracted, completeness:
+    extracted -> simplified -- thresholds of half a lattice spacing and one, in world units; plus spacing (the largest of the
+    three axes') and, under in_spacings, the distances divided by it.  The distances are between samples, so they do not fall
+    below the spacing of the samples themselves: sampling_floor holds chamfer and hausdorff of the extracted mesh against ITSELF
+    from the same two sets of `samples` points (world units, and in_spacings) -- what a simplification without any error would
+    score.  None when either mesh has no face."""
+    from . import mesh_distance
+    if faces.shape[0] == 0 or faces_0.shape[0] == 0:
+        return None
+    lo, hi = _box(lo, hi)
+    spacing = max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(res)))
+    out = mesh_distance.compare(verts, faces, verts_0, faces_0, samples, seed, (0.5 * spacing, spacing))
+    floor = mesh_distance.compare(verts_0, faces_0, verts_0, faces_0, samples, seed)
+    per = lambda d: {k: v / spacing for k, v in d.items()}
+    out.update(spacing=spacing, in_spacings=dict(accuracy=per(out["accuracy"]), completeness=per(out["completeness"]),
+                                                 chamfer=out["chamfer"] / spacing, hausdorff=out["hausdorff"] / spacing),
+               sampling_floor=dict(chamfer=floor["chamfer"], hausdorff=floor["hausdorff"],
+                                   in_spacings=dict(chamfer=floor["chamfer"] / spacing, hausdorff=floor["hausdorff"] / spacing)))
+    return out
+
+
 def vertex_normals(r, verts: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
     """(V, 3) float32: -grad sigma / |grad sigma| at the vertices (r.density_gradient: arch ngp; arch mlp raises
     NotImplementedError); a zero gradient gives a zero normal"""
@@ -253,15 +280,18 @@ def write_ply(path: str, verts, faces, normals=None) -> None:
 
 def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None,
            normals: bool = True, min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False,
-           simplify: Optional[float] = None) -> dict:
+           simplify: Optional[float] = None, simplify_error: Optional[int] = None) -> dict:
     """sample, (clean,) extract, (simplify,) (normals,) write `path`; the box defaults to the renderer's cfg.aabb.
     -> dict(verts=V, faces=F, resolution=(nx, ny, nz), normals=bool); with min_points > 1, largest or fill_cavities the lattice
     goes through `clean` first and the dict carries its stats as well.  With `simplify` = k >= 1 the extracted mesh goes
     through `simplify` on the grid `cluster_grid(res, k)` -- clusters of k lattice spacings -- before the normals are taken
     at the new positions; the dict then carries its stats (clusters, degenerate, duplicate, orphans), cluster_grid, and the
-    counts before the simplification as extracted_verts / extracted_faces."""
+    counts before the simplification as extracted_verts / extracted_faces.  With `simplify_error` = n as well the simplified
+    mesh is scored against the extracted one, n samples a surface (`simplification_error`), under the key simplify_error."""
     _rule(min_points, largest)
     grid = None if simplify is None else cluster_grid(res, simplify)
+    if simplify_error is not None and (grid is None or int(simplify_error) != simplify_error or simplify_error < 1):
+        raise ValueError(f"mesh.export: simplify_error is a number of samples >= 1 and needs simplify; got {simplify_error!r}")
     aabb = [float(v) for v in r.cfg.aabb]
     lo = aabb[:3] if lo is None else lo
     hi = aabb[3:] if hi is None else hi
@@ -277,8 +307,12 @@ def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] =
     simplified = {}
     if grid is not None:
         extracted = dict(extracted_verts=int(verts.shape[0]), extracted_faces=int(faces.shape[0]))
+        before = verts, faces
         verts, faces, simplified = _simplify(verts, faces, lo, hi, grid)
         simplified = dict(simplified, cluster_grid=grid, **extracted)
+        if simplify_error is not None:
+            simplified["simplify_error"] = simplification_error(verts, faces, *before, lo, hi, res, int(simplify_error))
+        del before
     nrm = vertex_normals(r, verts) if normals else None
     write_ply(path, verts, faces, nrm)
     return dict(verts=int(verts.shape[0]), faces=int(faces.shape[0]), resolution=res, normals=bool(normals), **cleaned, **simplified)

@@ -1066,6 +1066,54 @@ def mesh_simplify_compact_faces(ids: torch.Tensor, keep: torch.Tensor, foff: tor
     return faces
 
 
+# ------------------------------------------------------------------------------- mesh distance (grid nearest neighbour)
+NN_MAX_EXTENT = 512                  # include/ren_amd.h REN_NN_MAX_EXTENT
+
+
+def _nn_grid(lo: Sequence[float], h: float, grid: Sequence[int], what: str):
+    """-> (lo as float[3], h and its reciprocal as the float32 values the kernels get, the extents)"""
+    lo = [float(v) for v in lo]
+    if len(lo) != 3 or not all(math.isfinite(v) and abs(v) <= 3.4028234663852886e38 for v in lo):
+        raise ValueError(f"{what}: lo is three finite float32 values; got {lo}")
+    g = tuple(grid)
+    if len(g) != 3 or any(int(v) != v or not 1 <= v <= NN_MAX_EXTENT for v in g):
+        raise ValueError(f"{what}: the grid is three integers in [1, {NN_MAX_EXTENT}]; got {grid!r}")
+    h32 = ctypes.c_float(float(h)).value
+    if not (math.isfinite(h32) and 2.0 ** -100 <= h32 <= 2.0 ** 100):
+        raise ValueError(f"{what}: the cell edge h must be a float32 in [2^-100, 2^100]; got {h!r}")
+    return (ctypes.c_float * 3)(*lo), h32, ctypes.c_float(1.0 / h32).value, tuple(int(v) for v in g)
+
+
+def nn_cells(pts: torch.Tensor, lo: Sequence[float], h: float, grid: Sequence[int]) -> torch.Tensor:
+    """pts (n, 3) float32 -> cell (n,) int32: the linear id (z * gy + y) * gx + x of each point's cell in the grid of cubic
+    cells of edge h from the corner lo, per axis clamp(floor((p - lo) * float32(1 / h)), 0, g - 1) in float32 (include/ren_amd.h
+    "mesh distance").  n == 0 launches nothing."""
+    plo, _, inv_h, g = _nn_grid(lo, h, grid, "nn_cells")
+    n = _rows(pts, 3, "nn_cells: pts")
+    pp = _ptr(pts, torch.float32)
+    cell = torch.empty(n, device=pts.device, dtype=torch.int32)
+    check(_lib.load().ren_nn_cells(pp, n, plo, _f(inv_h), *g, _ptr(cell), _stream()), "ren_nn_cells")
+    return cell
+
+
+def nn_search(queries: torch.Tensor, ref_records: torch.Tensor, cell_start: torch.Tensor, lo: Sequence[float], h: float,
+              grid: Sequence[int]):
+    """queries (nq, 3) float32; ref_records (nr, 4) float32: the references grouped by their nn_cells id, row = (x, y, z, the
+    bits of the original index); cell_start (gx gy gz + 1,) int32: the records of cell c are [cell_start[c], cell_start[c + 1])
+    -> d2 (nq,) float32, idx (nq,) int32: the smallest float32 squared distance to a reference and the smallest original index
+    that attains it (include/ren_amd.h "mesh distance"), one query per lane in the given order.  nq == 0 launches nothing."""
+    plo, h32, inv_h, g = _nn_grid(lo, h, grid, "nn_search")
+    nq, nr = _rows(queries, 3, "nn_search: queries"), _rows(ref_records, 4, "nn_search: ref_records")
+    if cell_start.shape != (g[0] * g[1] * g[2] + 1,):
+        raise ValueError(f"nn_search: cell_start must be ({g[0] * g[1] * g[2] + 1},) for the grid {g}; got {tuple(cell_start.shape)}")
+    ptrs = (_ptr(queries, torch.float32), _ptr(ref_records, torch.float32), _ptr(cell_start, torch.int32))
+    d2 = torch.empty(nq, device=queries.device, dtype=torch.float32)
+    idx = torch.empty(nq, device=queries.device, dtype=torch.int32)
+    check(_lib.load().ren_nn_search(ptrs[0], nq, ptrs[1], ptrs[2], nr, plo, _f(h32), _f(inv_h), *g, _ptr(d2), _ptr(idx), _stream()),
+          "ren_nn_search")
+    return d2, idx
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 

@@ -2,7 +2,7 @@
 
     python scripts/export_mesh.py --config <YAML> --ckpt runs/train/last.ckpt --out mesh.ply \
         [--resolution N | --resolution NX NY NZ] [--level L] [--aabb x0 y0 z0 x1 y1 z1] [--no-normals]
-        [--min-component N] [--largest K] [--fill-cavities] [--simplify K]
+        [--min-component N] [--largest K] [--fill-cavities] [--simplify K [--simplify-error [N]]]
 
 The field is loaded as scripts/render.py loads it.  The density is sampled on a regular lattice of --resolution points per
 axis over --aabb (default: the model's box), the surface sigma = --level is extracted on the GPU (robust_e_nerf_amd/mesh.py)
@@ -10,7 +10,8 @@ and every vertex gets the direction of -grad sigma as its normal, the convention
 density gradient: its mesh is written without normals.  --min-component / --largest drop floaters (connected pieces of the
 solid, counted in lattice points) and --fill-cavities closes the voids inside objects before the extraction (mesh.clean).
 --simplify K merges the vertices within each cell of K lattice spacings into one (vertex clustering, mesh.simplify): sample
-finely for the geometry, simplify for a file a viewer can hold.  `model.nerf.aabb: auto` spans the camera positions, so it needs
+finely for the geometry, simplify for a file a viewer can hold; --simplify-error scores the simplified mesh against the extracted
+one (N samples a surface, default 1 000 000: mesh_distance.compare) in world units and in lattice spacings.  `model.nerf.aabb: auto` spans the camera positions, so it needs
 --dataset-dir, --synthetic or an explicit --aabb.
 """
 import argparse
@@ -45,6 +46,9 @@ def parse_args(argv=None):
                     help="fill the voids that reach no face of the lattice: no inner surface of a hollow object")
     ap.add_argument("--simplify", type=float, metavar="K",
                     help="simplify the mesh by vertex clustering: one vertex per cell of K lattice spacings, K >= 1 (default: off)")
+    ap.add_argument("--simplify-error", type=int, nargs="?", const=1_000_000, metavar="N",
+                    help="with --simplify: the distance between the simplified and the extracted mesh from N samples a surface "
+                         "(default 1000000) (default: off)")
     ap.add_argument("--dataset-dir", help="camera poses for `aabb: auto` (default: the YAML's data.dataset_directory)")
     ap.add_argument("--synthetic", action="store_true", help="`aabb: auto` from the synthetic benchmark orbit")
     args = ap.parse_args(argv)
@@ -54,6 +58,8 @@ def parse_args(argv=None):
         ap.error("--min-component and --largest take integers >= 1")
     if args.simplify is not None and not (math.isfinite(args.simplify) and args.simplify >= 1):
         ap.error("--simplify takes a finite number >= 1")
+    if args.simplify_error is not None and (args.simplify is None or args.simplify_error < 1):
+        ap.error("--simplify-error takes a number of samples >= 1 and needs --simplify")
     args.resolution = tuple(args.resolution * 3 if len(args.resolution) == 1 else args.resolution)
     return args
 
@@ -85,7 +91,8 @@ def main(argv=None):
     lo, hi = (args.aabb[:3], args.aabb[3:]) if args.aabb else (None, None)
     t0 = time.perf_counter()
     stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals, min_points=args.min_component,
-                        largest=args.largest, fill_cavities=args.fill_cavities, simplify=args.simplify)
+                        largest=args.largest, fill_cavities=args.fill_cavities, simplify=args.simplify,
+                        **({} if args.simplify_error is None else dict(simplify_error=args.simplify_error)))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{stats['verts']} vertices, {stats['faces']} faces ({'with' if normals else 'no'} normals) at resolution "
@@ -97,6 +104,16 @@ def main(argv=None):
         print(f"simplified from {stats['extracted_verts']} vertices, {stats['extracted_faces']} faces on a cluster grid of "
               f"{' x '.join(str(v) for v in stats['cluster_grid'])}: {stats['clusters']} clusters, {stats['degenerate']} collapsed and "
               f"{stats['duplicate']} repeated faces dropped, {stats['orphans']} unreferenced vertices removed", flush=True)
+    err = stats.get("simplify_error")
+    if err:
+        u = err["in_spacings"]
+        print(f"simplification error from {err['samples']} samples a surface, in lattice spacings of {err['spacing']:.6g} (world units): "
+              f"simplified -> extracted mean {u['accuracy']['mean']:.4f} ({err['accuracy']['mean']:.6g}), max {u['accuracy']['max']:.4f}; "
+              f"extracted -> simplified mean {u['completeness']['mean']:.4f} ({err['completeness']['mean']:.6g}), "
+              f"max {u['completeness']['max']:.4f}; Chamfer {u['chamfer']:.4f}, Hausdorff {u['hausdorff']:.4f} ({err['hausdorff']:.6g}); "
+              f"the extracted mesh against itself from the same samples: Chamfer {err['sampling_floor']['in_spacings']['chamfer']:.4f}, "
+              f"Hausdorff {err['sampling_floor']['in_spacings']['hausdorff']:.4f} (the floor the sampling sets: more samples lower it)",
+              flush=True)
 
 
 if __name__ == "__main__":

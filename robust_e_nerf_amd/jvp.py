@@ -19,6 +19,8 @@ def trajectory_jvp(ts, tab_ts, tab_pos, tab_quat):
     B, dev = ts.shape[0], ts.device
     pos, dpos = torch.empty(B, 3, device=dev), torch.empty(B, 3, device=dev)
     rot, drot = torch.empty(B, 3, 3, device=dev), torch.empty(B, 3, 3, device=dev)
+    if B == 0:                                           # empty tensors have no storage: their null pointers are no bad arguments
+        return pos, rot, dpos, drot
     check(_lib.load().ren_trajectory_jvp(_ptr(ts, torch.float64), B, _ptr(tab_ts, torch.int64), _ptr(tab_pos),
                                          _ptr(tab_quat), tab_ts.shape[0], _ptr(pos), _ptr(rot), _ptr(dpos),
                                          _ptr(drot), _stream()), "ren_trajectory_jvp")
@@ -28,6 +30,8 @@ def trajectory_jvp(ts, tab_ts, tab_pos, tab_quat):
 def raygen_jvp(Kinv, px, pos, rot, dpos, drot):
     B, dev = px.shape[0], px.device
     o, d, od, dd = (torch.empty(B, 3, device=dev) for _ in range(4))
+    if B == 0:
+        return o, d, od, dd
     check(_lib.load().ren_raygen_jvp(_ptr(Kinv), _ptr(px), _ptr(pos), _ptr(rot), _ptr(dpos), _ptr(drot), B,
                                      _ptr(o), _ptr(d), _ptr(od), _ptr(dd), _stream()), "ren_raygen_jvp")
     return o, d, od, dd
@@ -38,6 +42,8 @@ def trajectory_jvp2(ts, tab_ts, tab_pos, tab_quat):
     B, dev = ts.shape[0], ts.device
     pos, dpos = torch.empty(B, 3, device=dev), torch.empty(B, 3, device=dev)
     rot, drot, ddrot = (torch.empty(B, 3, 3, device=dev) for _ in range(3))
+    if B == 0:
+        return pos, rot, dpos, drot, ddrot
     check(_lib.load().ren_trajectory_jvp2(_ptr(ts, torch.float64), B, _ptr(tab_ts, torch.int64), _ptr(tab_pos),
                                           _ptr(tab_quat), tab_ts.shape[0], _ptr(pos), _ptr(rot), _ptr(dpos),
                                           _ptr(drot), _ptr(ddrot), _stream()), "ren_trajectory_jvp2")
@@ -47,6 +53,8 @@ def trajectory_jvp2(ts, tab_ts, tab_pos, tab_quat):
 def raygen_jvp2(Kinv, px, pos, rot, dpos, drot, ddrot):
     B, dev = px.shape[0], px.device
     o, d, od, dd, ddd = (torch.empty(B, 3, device=dev) for _ in range(5))
+    if B == 0:
+        return o, d, od, dd, ddd
     check(_lib.load().ren_raygen_jvp2(_ptr(Kinv), _ptr(px), _ptr(pos), _ptr(rot), _ptr(dpos), _ptr(drot),
                                       _ptr(ddrot), B, _ptr(o), _ptr(d), _ptr(od), _ptr(dd), _ptr(ddd), _stream()),
           "ren_raygen_jvp2")

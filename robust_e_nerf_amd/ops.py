@@ -182,6 +182,8 @@ def trajectory(ts: torch.Tensor, tab_ts, tab_pos, tab_quat):
     B = ts.shape[0]
     pos = torch.empty(B, 3, device=ts.device, dtype=torch.float32)
     rot = torch.empty(B, 3, 3, device=ts.device, dtype=torch.float32)
+    if B == 0:                                           # empty tensors have no storage: their null pointers are no bad arguments
+        return pos, rot
     check(_lib.load().ren_trajectory_fwd(_ptr(ts, torch.float64), B, _ptr(tab_ts, torch.int64),
                                          _ptr(tab_pos, torch.float32), _ptr(tab_quat, torch.float32),
                                          tab_ts.shape[0], _ptr(pos), _ptr(rot), _stream()), "ren_trajectory_fwd")
@@ -192,6 +194,8 @@ def raygen(Kinv, px, pos, rot):
     B = px.shape[0]
     o = torch.empty(B, 3, device=px.device, dtype=torch.float32)
     d = torch.empty(B, 3, device=px.device, dtype=torch.float32)
+    if B == 0:
+        return o, d
     check(_lib.load().ren_raygen_fwd(_ptr(Kinv, torch.float32), _ptr(px, torch.float32), _ptr(pos, torch.float32),
                                      _ptr(rot, torch.float32), B, _ptr(o), _ptr(d), _stream()), "ren_raygen_fwd")
     return o, d
@@ -202,6 +206,8 @@ def pose_rays(ts, px, Kinv, tab_ts, tab_pos, tab_quat):
     R = ts.shape[0]
     o = torch.empty(R, 3, device=ts.device, dtype=torch.float32)
     d = torch.empty(R, 3, device=ts.device, dtype=torch.float32)
+    if R == 0:
+        return o, d
     check(_lib.load().ren_pose_rays_fwd(_ptr(ts, torch.float64), R, _ptr(px, torch.float32), px.shape[0], _ptr(Kinv, torch.float32),
                                         _ptr(tab_ts, torch.int64), _ptr(tab_pos, torch.float32), _ptr(tab_quat, torch.float32),
                                         tab_ts.shape[0], _ptr(o), _ptr(d), _stream()), "ren_pose_rays_fwd")

@@ -1044,6 +1044,42 @@ int ren_nn_cells(const float *pts, int64_t n, const float *lo, float inv_h, int3
 int ren_nn_search(const float *queries, int64_t nq, const float *ref_records, const int32_t *cell_start, int64_t nr,
                   const float *lo, float h, float inv_h, int32_t gx, int32_t gy, int32_t gz, float *d2, int32_t *idx, void *stream);
 
+/* ---- tsdf (csrc/ren_tsdf.hip) -------------------------------------------------------------------------- *
+ * Fusion of posed z-depth maps into a truncated signed distance lattice: what a mesh of the RENDERED surface is extracted from.
+ * Lattice nx x ny x nz, linear index p = (i * ny + j) * nz + k as in "mesh"; per point sum[p] (float32) and count[p] (int32),
+ * READ AND UPDATED: the caller zeroes both before the first call, and a further call with further views continues the same
+ * sums.  The views run in ascending order and every point adds its terms in that order, so the result does not depend on how
+ * a sequence of views is split into calls, and it repeats bit for bit.
+ *   depth (V, H, W) float32, device: z-depth along the optical axis; +inf = the ray met nothing, NaN or <= 0 = no information.
+ *   cams (V, 12) float32, device: per view the centre c[3], then the camera-to-world rotation R[9] row-major (pos / rot of
+ *     ren_raygen_fwd: column a of R is camera axis a, axis 2 looks forward).
+ *   K5: five floats on the HOST, k00, k01, k02, k11, k12 of the upper-triangular pinhole matrix.
+ *   lo, step: three float64 each on the HOST; step_a = (hi_a - lo_a) / (n_a - 1), formed by the caller in float64.
+ * Per point and view, float32, every operation rounded on its own (no FMA), IEEE division:
+ *   1. x_a = float32(lo_a + double(idx_a) * step_a): float64, the product and the sum rounded once each, then one rounding
+ *   2. d_a = x_a - c_a
+ *   3. q_a = (R[0][a] * d_0 + R[1][a] * d_1) + R[2][a] * d_2
+ *   4. z = q_2; the view is skipped unless z > z_min (NaN skips)
+ *   5. xn = q_0 / z, yn = q_1 / z
+ *   6. u = (k00 * xn + k01 * yn) + k02, v = k11 * yn + k12
+ *   7. fu = floorf(u + 0.5f), fv = floorf(v + 0.5f); skipped unless 0 <= fu < W and 0 <= fv < H (NaN skips): the nearest pixel,
+ *      pixel (x, y) at the integer coordinates (x, y)
+ *   8. D = depth[view][int(fv)][int(fu)]; skipped if D is NaN or D <= 0
+ *   9. s = D - z; skipped if s < -trunc: the point is hidden behind the surface this view saw
+ *  10. t = (s >= trunc) ? 1.0f : s / trunc (+inf gives 1)
+ *  11. sum[p] += t, count[p] += 1
+ * One launch, one lattice point per lane; the 12 floats of REN_TSDF_VIEW_BATCH views at a time are staged in LDS per workgroup.
+ * No atomics.  V == 0 (or H * W == 0: every view skips every point) launches nothing.
+ * REN_ERR_BAD_ARG before any launch for V, H or W negative, H or W above REN_TSDF_MAX_IMAGE, V * H * W of 2^31 and beyond, a
+ * lattice extent below 2 or more than REN_MESH_MAX_POINTS points, trunc or z_min not positive and finite, lo or step not
+ * finite, a step that is not positive, a null pointer that a positive count needs (K5, lo, step, sum and count always; cams
+ * with V > 0; depth with V * H * W > 0), a pointer not aligned to its element. */
+#define REN_TSDF_VIEW_BATCH 16               /* views whose cameras one workgroup stages in LDS at a time */
+#define REN_TSDF_MAX_IMAGE 16384             /* H and W at most: pixel coordinates are exact in float32 */
+int ren_tsdf_integrate(const float *depth, int32_t V, int32_t H, int32_t W, const float *cams, const float *K5, const double *lo,
+                       const double *step, int32_t nx, int32_t ny, int32_t nz, float trunc, float z_min, float *sum, int32_t *count,
+                       void *stream);
+
 /* ---- utilities ------------------------------------------------------------------------------------- */
 /* out[c] = sum_r in[r*C + c]  (C <= 4); scratch512: 512 floats of device scratch (two-stage, deterministic) */
 int ren_column_sum(const float *in, int64_t rows, int32_t C, float *out, float *scratch512, void *stream);

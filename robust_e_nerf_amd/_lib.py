@@ -179,6 +179,8 @@ SIGNATURES = {
     "ren_mesh_simplify_compact_faces": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P]),
     "ren_nn_cells": (c_int, [P, c_int64, POINTER(c_float), c_float, c_int32, c_int32, c_int32, P, P]),
     "ren_nn_search": (c_int, [P, c_int64, P, P, c_int64, POINTER(c_float), c_float, c_float, c_int32, c_int32, c_int32, P, P, P]),
+    "ren_tsdf_integrate": (c_int, [P, c_int32, c_int32, c_int32, P, POINTER(c_float), POINTER(c_double), POINTER(c_double), c_int32,
+                                   c_int32, c_int32, c_float, c_float, P, P, P]),
 }
 
 _lib = None

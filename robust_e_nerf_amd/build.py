@@ -19,7 +19,8 @@ SOURCES = ["ren_api.hip", "ren_pose.hip", "ren_sampling.hip", "ren_composite.hip
            "ren_hashgrid.hip", "ren_hashgrid_binned.hip", "ren_mlp.hip", "ren_jvp.hip", "ren_mlp_jvp.hip",
            "ren_jvp2.hip", "ren_dense.hip", "ren_vfield.hip", "ren_mlp_x.hip", "ren_mlp_jvp_x.hip",
            "ren_metrics.hip", "ren_normals.hip", "ren_event_frames.hip", "ren_event_table.hip", "ren_mesh.hip",
-           "ren_mesh_components.hip", "ren_mesh_simplify.hip", "ren_event_filter.hip", "ren_mesh_distance.hip"]
+           "ren_mesh_components.hip", "ren_mesh_simplify.hip", "ren_event_filter.hip", "ren_mesh_distance.hip",
+           "ren_tsdf.hip"]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           "-Wno-unused-result"]
 # the sampler must match the sequential oracle bit for bit: no FMA contraction there
@@ -53,7 +54,9 @@ PER_FILE = {"ren_sampling.hip": ["-ffp-contract=off"] + NO_SLP, "ren_jvp2.hip": 
             # the cluster positions are held to a float64 restatement bit for bit: every operation rounded on its own
             "ren_mesh_simplify.hip": ["-ffp-contract=off"] + NO_SLP,
             # the squared distances are held to a float32 restatement bit for bit: every operation rounded on its own
-            "ren_mesh_distance.hip": ["-ffp-contract=off"] + NO_SLP}
+            "ren_mesh_distance.hip": ["-ffp-contract=off"] + NO_SLP,
+            # the projections are held to a float32 restatement bit for bit: every operation rounded on its own
+            "ren_tsdf.hip": ["-ffp-contract=off"] + NO_SLP}
 
 
 def _headers():

@@ -397,6 +397,29 @@ def load_calibration(root: str) -> Dict[str, object]:
     return out
 
 
+def load_trajectory_camera(root: Optional[str] = None, synthetic_scene=None, height: Optional[int] = None,
+                           width: Optional[int] = None):
+    """the camera a script renders along its trajectory (scripts/render.py, scripts/export_mesh.py --tsdf): the dataset's
+    camera_poses.npz and camera_calibration.npz at the calibration's image size, or -- with `synthetic_scene`, the benchmark's
+    (ts, pos, quat, Kinv) arrays -- the synthetic orbit at 260 x 346; `height` / `width` override the size
+    -> (tab_ts i64 (C,), tab_pos f32 (C, 3), tab_quat XYZW f32 (C, 4), Kinv f32 (3, 3), height, width)"""
+    if synthetic_scene is not None:
+        tab_ts, tab_pos, tab_quat, Kinv = (torch.from_numpy(a) for a in synthetic_scene)
+        return tab_ts, tab_pos, tab_quat, Kinv, height or 260, width or 346
+    tab_ts, tab_pos, tab_quat = load_camera_poses(root)
+    Kinv = load_calibration(root)["Kinv"]
+    raw = np.load(os.path.join(root, CAMERA_CALIBRATION))
+    return tab_ts, tab_pos, tab_quat, Kinv, height or int(raw["img_height"]), width or int(raw["img_width"])
+
+
+def even_view_times(tab_ts: torch.Tensor, n: int) -> torch.Tensor:
+    """n timestamps (float64 ns) evenly spaced in time over the trajectory's span, both ends included; n = 1 gives its start"""
+    if n < 1:
+        raise ValueError(f"even_view_times: n >= 1; got {n}")
+    t0, t1 = float(tab_ts[0]), float(tab_ts[-1])
+    return torch.tensor([t0 + (t1 - t0) * (k / (n - 1) if n > 1 else 0.0) for k in range(n)], dtype=torch.float64)
+
+
 # ------------------------------------------------------------------------------------------- posed images
 # The reference's validation / test data: `PosedImage` (robust_e_nerf/data/datasets.py:376-690) -- NeRF-synthetic style
 # `views/transforms_{stage}.json` (in the dataset directory or one level above it) with OpenGL camera-to-world matrices,

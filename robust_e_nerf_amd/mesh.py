@@ -288,17 +288,33 @@ def export(r, path: str, res: Res, level: float, lo: Optional[Sequence[float]] =
     at the new positions; the dict then carries its stats (clusters, degenerate, duplicate, orphans), cluster_grid, and the
     counts before the simplification as extracted_verts / extracted_faces.  With `simplify_error` = n as well the simplified
     mesh is scored against the extracted one, n samples a surface (`simplification_error`), under the key simplify_error."""
-    _rule(min_points, largest)
-    grid = None if simplify is None else cluster_grid(res, simplify)
-    if simplify_error is not None and (grid is None or int(simplify_error) != simplify_error or simplify_error < 1):
-        raise ValueError(f"mesh.export: simplify_error is a number of samples >= 1 and needs simplify; got {simplify_error!r}")
+    grid = export_options(res, min_points, largest, simplify, simplify_error)
     aabb = [float(v) for v in r.cfg.aabb]
     lo = aabb[:3] if lo is None else lo
     hi = aabb[3:] if hi is None else hi
     res = _resolution(res)
     if math.isnan(float(level)):
         raise ValueError("mesh.export: level is NaN")
-    sigma = sample_density(r, lo, hi, res)
+    return export_lattice(r, path, sample_density(r, lo, hi, res), level, lo, hi, normals, min_points, largest, fill_cavities,
+                          grid, simplify_error)
+
+
+def export_options(res: Res, min_points: int, largest: Optional[int], simplify: Optional[float], simplify_error: Optional[int]):
+    """`export`'s checks that need no lattice, before anything is sampled or rendered -> the cluster grid of `simplify`, or None"""
+    _rule(min_points, largest)
+    grid = None if simplify is None else cluster_grid(res, simplify)
+    if simplify_error is not None and (grid is None or int(simplify_error) != simplify_error or simplify_error < 1):
+        raise ValueError(f"mesh.export: simplify_error is a number of samples >= 1 and needs simplify; got {simplify_error!r}")
+    return grid
+
+
+def export_lattice(r, path: str, sigma: torch.Tensor, level: float, lo: Sequence[float], hi: Sequence[float], normals: bool = True,
+                   min_points: int = 1, largest: Optional[int] = None, fill_cavities: bool = False,
+                   grid: Optional[Tuple[int, int, int]] = None, simplify_error: Optional[int] = None) -> dict:
+    """the tail of `export` for any lattice sigma (nx, ny, nz) float32 over [lo, hi] -- the sampled density, or the fused field
+    of tsdf.export at level 0: (clean,) extract at `level`, (simplify on the cluster grid `grid`,) (normals from r,) write
+    `path` -> `export`'s dict"""
+    res = tuple(int(n) for n in sigma.shape)
     cleaned = {}
     if min_points > 1 or largest is not None or fill_cavities:
         sigma, cleaned = clean(sigma, level, min_points, largest, fill_cavities)

@@ -1120,6 +1120,54 @@ def nn_search(queries: torch.Tensor, ref_records: torch.Tensor, cell_start: torc
     return d2, idx
 
 
+# ------------------------------------------------------------------------------- tsdf (fusion of depth maps into a lattice)
+TSDF_VIEW_BATCH = 16                 # include/ren_amd.h REN_TSDF_VIEW_BATCH
+TSDF_MAX_IMAGE = 16384               # include/ren_amd.h REN_TSDF_MAX_IMAGE
+
+
+def _pos_f32(v, what: str) -> float:
+    v32 = ctypes.c_float(float(v)).value
+    if not (math.isfinite(v32) and v32 > 0):
+        raise ValueError(f"{what} must be a positive finite float32; got {v!r}")
+    return v32
+
+
+def tsdf_integrate(depth: torch.Tensor, cams: torch.Tensor, K, lo: Sequence[float], hi: Sequence[float], res: Sequence[int],
+                   trunc: float, z_min: float, sum: torch.Tensor, count: torch.Tensor) -> None:
+    """depth (V, H, W) float32 z-depth maps (+inf: nothing met; NaN or <= 0: no information), cams (V, 12) float32 (centre, then
+    the camera-to-world rotation row-major), K the 3 x 3 upper-triangular pinhole matrix (a tensor or nested sequence; k00, k01,
+    k02, k11, k12 are read), the lattice of `res` = (nx, ny, nz) points over the box [lo, hi] -> sum (nx, ny, nz) float32 and
+    count (nx, ny, nz) int32 UPDATED IN PLACE: per point and view, the truncated signed distance D - z over trunc, 1 at and
+    beyond trunc, skipped below -trunc, at the nearest pixel (include/ren_amd.h "tsdf").  V == 0 launches nothing."""
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"tsdf_integrate: the box needs finite lo < hi on every axis; got {lo}, {hi}")
+    r = tuple(res)
+    if len(r) != 3 or any(int(v) != v or v < 2 for v in r):
+        raise ValueError(f"tsdf_integrate: the resolution is three integers >= 2; got {res!r}")
+    r = tuple(int(v) for v in r)
+    if r[0] * r[1] * r[2] > MESH_MAX_POINTS:
+        raise ValueError(f"tsdf_integrate: a lattice of {r} has more than 2^30 points")
+    if depth.dim() != 3 or cams.dim() != 2 or cams.shape != (depth.shape[0], 12):
+        raise ValueError(f"tsdf_integrate: depth must be (V, H, W) and cams (V, 12); got {tuple(depth.shape)}, {tuple(cams.shape)}")
+    n_views, height, width = (int(v) for v in depth.shape)
+    if height > TSDF_MAX_IMAGE or width > TSDF_MAX_IMAGE or n_views * height * width >= 2 ** 31:
+        raise ValueError(f"tsdf_integrate: images of at most {TSDF_MAX_IMAGE} pixels a side and fewer than 2^31 pixels a call; "
+                         f"got {tuple(depth.shape)}")
+    if tuple(sum.shape) != r or tuple(count.shape) != r:
+        raise ValueError(f"tsdf_integrate: sum and count must be {r}; got {tuple(sum.shape)}, {tuple(count.shape)}")
+    k = torch.as_tensor(K, dtype=torch.float32).cpu()
+    if k.shape != (3, 3):
+        raise ValueError(f"tsdf_integrate: K must be 3 x 3; got {tuple(k.shape)}")
+    k5 = (ctypes.c_float * 5)(float(k[0, 0]), float(k[0, 1]), float(k[0, 2]), float(k[1, 1]), float(k[1, 2]))
+    trunc, z_min = _pos_f32(trunc, "tsdf_integrate: trunc"), _pos_f32(z_min, "tsdf_integrate: z_min")
+    ptrs = (_ptr(depth, torch.float32), _ptr(cams, torch.float32), _ptr(sum, torch.float32), _ptr(count, torch.int32))
+    d3 = ctypes.c_double * 3
+    step = [(b - a) / (n - 1) for a, b, n in zip(lo, hi, r)]
+    check(_lib.load().ren_tsdf_integrate(ptrs[0], n_views, height, width, ptrs[1], k5, d3(*lo), d3(*step), *r, _f(trunc), _f(z_min),
+                                         ptrs[2], ptrs[3], _stream()), "ren_tsdf_integrate")
+
+
 # ------------------------------------------------------------------------------- loss / optimiser
 ERR_FN ={"l1": 0, "mse": 1, "mape": 2}
 

@@ -3,6 +3,7 @@
     python scripts/export_mesh.py --config <YAML> --ckpt runs/train/last.ckpt --out mesh.ply \
         [--resolution N | --resolution NX NY NZ] [--level L] [--aabb x0 y0 z0 x1 y1 z1] [--no-normals]
         [--min-component N] [--largest K] [--fill-cavities] [--simplify K [--simplify-error [N]]]
+        [--tsdf [--tsdf-views N] [--tsdf-trunc T] [--tsdf-min-opacity A] [--tsdf-carve]]
 
 The field is loaded as scripts/render.py loads it.  The density is sampled on a regular lattice of --resolution points per
 axis over --aabb (default: the model's box), the surface sigma = --level is extracted on the GPU (robust_e_nerf_amd/mesh.py)
@@ -13,6 +14,11 @@ solid, counted in lattice points) and --fill-cavities closes the voids inside ob
 finely for the geometry, simplify for a file a viewer can hold; --simplify-error scores the simplified mesh against the extracted
 one (N samples a surface, default 1 000 000: mesh_distance.compare) in world units and in lattice spacings.  `model.nerf.aabb: auto` spans the camera positions, so it needs
 --dataset-dir, --synthetic or an explicit --aabb.
+--tsdf meshes what the field renders instead of a density level: --tsdf-views poses evenly spaced in time along the trajectory
+(the dataset's, or the synthetic orbit) are rendered at the calibration's intrinsics and size, their z-depth maps are fused into
+a truncated signed distance lattice on the GPU and its zero set is extracted (robust_e_nerf_amd/tsdf.py); everything after the
+extraction is the same.  Points farther than the truncation behind every surface are never seen, so a closed object carries an
+inner shell at about that depth; it is a cavity, and --fill-cavities removes it.
 """
 import argparse
 import math
@@ -26,7 +32,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def parse_args(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", required=True)
     ap.add_argument("--ckpt", help="checkpoint to load (default: the YAML's model.checkpoint_filepath)")
@@ -50,7 +56,28 @@ def parse_args(argv=None):
                     help="with --simplify: the distance between the simplified and the extracted mesh from N samples a surface "
                          "(default 1000000) (default: off)")
     ap.add_argument("--dataset-dir", help="camera poses for `aabb: auto` (default: the YAML's data.dataset_directory)")
-    ap.add_argument("--synthetic", action="store_true", help="`aabb: auto` from the synthetic benchmark orbit")
+    ap.add_argument("--synthetic", action="store_true",
+                    help="`aabb: auto` from the synthetic benchmark orbit; with --tsdf also the views' poses and intrinsics")
+    ap.add_argument("--tsdf", action="store_true",
+                    help="mesh what the field RENDERS instead of a density level: z-depth maps of --tsdf-views posed views are fused "
+                         "into a truncated signed distance lattice and its zero set is extracted (robust_e_nerf_amd/tsdf.py); "
+                         "--level is ignored.  Points farther than the truncation behind every surface are never seen, so a closed "
+                         "object carries an inner shell at about that depth: --fill-cavities removes it")
+    ap.add_argument("--tsdf-views", type=int, default=64, metavar="N",
+                    help="with --tsdf: N poses evenly spaced in time along the trajectory, at the calibration's intrinsics and size "
+                         "(default 64)")
+    ap.add_argument("--tsdf-trunc", type=float, metavar="T",
+                    help="with --tsdf: the truncation distance in world units (default: three times the largest lattice spacing)")
+    ap.add_argument("--tsdf-min-opacity", type=float, default=0.5, metavar="A",
+                    help="with --tsdf: a pixel whose rendered opacity is below A has no depth (default 0.5)")
+    ap.add_argument("--tsdf-carve", action="store_true",
+                    help="with --tsdf: a pixel below --tsdf-min-opacity met nothing, so the points along its ray are free space "
+                         "(default: it says nothing about them)")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one value or three")
@@ -60,6 +87,14 @@ def parse_args(argv=None):
         ap.error("--simplify takes a finite number >= 1")
     if args.simplify_error is not None and (args.simplify is None or args.simplify_error < 1):
         ap.error("--simplify-error takes a number of samples >= 1 and needs --simplify")
+    if args.tsdf_views < 1:
+        ap.error("--tsdf-views takes an integer >= 1")
+    if args.tsdf_trunc is not None and not (math.isfinite(args.tsdf_trunc) and args.tsdf_trunc > 0):
+        ap.error("--tsdf-trunc takes a finite number > 0")
+    if not 0.0 <= args.tsdf_min_opacity <= 1.0:
+        ap.error("--tsdf-min-opacity takes a number in [0, 1]")
+    if args.tsdf and args.level != ap.get_default("level"):
+        print("warning: --level is ignored with --tsdf (the fused field is extracted at its zero set)", file=sys.stderr, flush=True)
     args.resolution = tuple(args.resolution * 3 if len(args.resolution) == 1 else args.resolution)
     return args
 
@@ -83,20 +118,42 @@ def main(argv=None):
     sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
     arch = ncfg.get("arch", "ngp")
     fld, r = config.make_renderer(ncfg, rcfg, checkpoint.radiance_dim(sd, arch), dev)
-    checkpoint.load_render_state(sd, fld, r, arch)
+    bkgd = checkpoint.load_render_state(sd, fld, r, arch)
     normals = not args.no_normals
     if normals and arch != "ngp":
         print(f"arch {arch} has no density gradient: the mesh is written without normals", flush=True)
         normals = False
     lo, hi = (args.aabb[:3], args.aabb[3:]) if args.aabb else (None, None)
+    common = dict(normals=normals, min_points=args.min_component, largest=args.largest, fill_cavities=args.fill_cavities,
+                  simplify=args.simplify, **({} if args.simplify_error is None else dict(simplify_error=args.simplify_error)))
     t0 = time.perf_counter()
-    stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, normals=normals, min_points=args.min_component,
-                        largest=args.largest, fill_cavities=args.fill_cavities, simplify=args.simplify,
-                        **({} if args.simplify_error is None else dict(simplify_error=args.simplify_error)))
+    if args.tsdf:
+        from robust_e_nerf_amd import ops, tsdf
+        if args.synthetic:
+            import bench
+            cam = data.load_trajectory_camera(None, bench.synthetic_scene())
+        else:
+            cam = data.load_trajectory_camera(args.dataset_dir or cfg["data"]["dataset_directory"])
+        tab_ts, tab_p, tab_q, Kinv, height, width = cam
+        ts = data.even_view_times(tab_ts, args.tsdf_views).to(dev)
+        cam_pos, cam_rot = ops.trajectory(ts, tab_ts.to(dev), tab_p.to(dev), tab_q.to(dev))
+        K = torch.linalg.inv(Kinv.double()).float()
+        stats = tsdf.export(r, args.out, K, Kinv.to(dev, torch.float32), cam_pos, cam_rot, height, width, args.resolution, lo, hi,
+                            trunc=args.tsdf_trunc, min_opacity=args.tsdf_min_opacity, carve=args.tsdf_carve, bkgd=bkgd, **common)
+        what = f"the zero set of {stats['views']} fused views of {height} x {width} (truncation {stats['trunc']:.6g})"
+    else:
+        stats = mesh.export(r, args.out, args.resolution, args.level, lo, hi, **common)
+        what = f"level {args.level:g}"
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{stats['verts']} vertices, {stats['faces']} faces ({'with' if normals else 'no'} normals) at resolution "
-          f"{' x '.join(str(v) for v in stats['resolution'])}, level {args.level:g}: {args.out} written in {dt:.2f} s", flush=True)
+          f"{' x '.join(str(v) for v in stats['resolution'])}, {what}: {args.out} written in {dt:.2f} s", flush=True)
+    if args.tsdf:
+        n_points = stats["resolution"][0] * stats["resolution"][1] * stats["resolution"][2]
+        print(f"{stats['observed']} of {n_points} lattice points were seen by a view", flush=True)
+        if not args.fill_cavities:
+            print("hint: a closed object carries an inner shell at a depth of about the truncation (what lies deeper is never "
+                  "seen); --fill-cavities removes it", flush=True)
     if "components" in stats:
         print(f"{stats['components']} connected pieces, {stats['kept']} kept ({stats['dropped_points']} lattice points dropped); "
               f"{stats['cavities']} cavities filled ({stats['filled_points']} lattice points)", flush=True)

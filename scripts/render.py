@@ -70,15 +70,10 @@ def main():
     dcfg, mcfg, ncfg = cfg["data"], cfg["model"], cfg["model"]["nerf"]
     if args.synthetic:
         import bench
-        tab_ts, tab_pos, tab_quat, Kinv = (torch.from_numpy(a) for a in bench.synthetic_scene())
-        height, width = args.height or 260, args.width or 346
+        tab_ts, tab_pos, tab_quat, Kinv, height, width = data.load_trajectory_camera(None, bench.synthetic_scene(), args.height, args.width)
     else:
         root = args.dataset_dir or dcfg["dataset_directory"]
-        tab_ts, tab_pos, tab_quat = data.load_camera_poses(root)
-        calib = data.load_calibration(root)
-        Kinv = calib["Kinv"]
-        raw = np.load(os.path.join(root, data.CAMERA_CALIBRATION))
-        height, width = args.height or int(raw["img_height"]), args.width or int(raw["img_width"])
+        tab_ts, tab_pos, tab_quat, Kinv, height, width = data.load_trajectory_camera(root, None, args.height, args.width)
     rcfg = config.render_cfg(cfg, tab_pos)
     sd = torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"]
     arch = ncfg.get("arch", "ngp")
